@@ -2,7 +2,13 @@
 """Headline benchmark: per_token_group_quant_fp8 + fp8_blockwise_scaled_mm at the Llama-3-8B FFN
 shape (BASELINE.json configs[1]: M=4096, N=14336, K=4096, 128-block scales) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: inputs, one clock ramp, W warm-up steps, EXACTLY K timed
+steps, the result line (`roofline` in it comes from the HIP events recorded inside those K steps). `--dump-outputs DIR` writes
+what the last timed step computed (dump_outputs below). `--full` adds every other leg: three repetitions of the timed region
+with the median reported, the same-run MFMA ceilings and in-kernel clock, the flash_mla_decode roofline, the `extra` legs and
+the CPU baseline.
 
 One "step" = one pass of the hot path over one synthetic batch already resident in HBM:
 quantise x[M,K] bf16 -> (e4m3, column-major 1x128 scales), then out = fp8_blockwise_scaled_mm(...)
@@ -12,8 +18,8 @@ so every rank runs an independent replica; rank 0 prints ONE JSON line. Without 
 `--gpus N` starts the N rank processes itself; under torch.distributed.run it uses the launcher's ranks.
 
 roofline.achieved is measured live with HIP events recorded on the launch stream around each GEMM
-launch of the timed region. cpu_baseline times the CPU oracle (torch eager, best of a few thread-pool widths) on a row
-sample of the same workload (rank 0, N=1 only).
+launch of the timed region. cpu_baseline (--full) times the CPU oracle (torch eager, best of a few thread-pool widths) on a
+row sample of the same workload (rank 0, N=1 only).
 """
 import argparse
 import json
@@ -38,7 +44,10 @@ GEMM_KERNEL = ("gemm_fp8bw_x32_kernel<bf16> (ONE launch: per workgroup three 256
 PMC_FILE = os.path.join("profiles", "r05", "bench_pmc.json")
 MLA_PMC_FILE = os.path.join("profiles", "r05", "mla_pmc.json")
 CLOCK_RAMP_S = 0.15  # untimed steady-state run of the step before the W warm-up steps
-REPS = 3             # repetitions of the timed region (each: ramp, W warm-up steps, exactly K timed steps)
+REPS = 3             # --full: repetitions of the timed region (each: ramp, W warm-up steps, exactly K timed steps); plain: one
+DUMP_SEED = 0xD0     # --dump-outputs: seed of the element samples
+DUMP_OUT_SAMPLE = 8 * 1024 * 1024  # elements of the GEMM output kept (32 MB as float32)
+DUMP_Q_SAMPLE = 4 * 1024 * 1024    # elements of the fp8 activations kept (16 MB as float32)
 BUILD_DIR = os.path.join(ROOT, "sgl-kernel-xpu_amd", "build")
 
 
@@ -51,6 +60,28 @@ def make_inputs(dev, seed):
     q = torch.empty(M, K, dtype=FP8, device=dev)
     s = torch.empty(K // GROUP, M, dtype=torch.float32, device=dev).t()  # column-major [M, K/128]
     return x, b, sb, q, s
+
+
+def dump_outputs(path, out, q, s):
+    """--dump-outputs: what the last timed step handed to its caller, as float32 .npy files (48.5 MB in all):
+      out.npy  the GEMM's bf16 result [M, N]: DUMP_OUT_SAMPLE elements at seeded flat indices (row-major, ascending)
+      q.npy    the quantised activations [M, K] (e4m3 values): DUMP_Q_SAMPLE elements, sampled the same way
+      s.npy    their 1x128 group scales [M, K/128], all of them
+    The indices come from DUMP_SEED alone and the inputs from make_inputs' seed, so two builds run with the same arguments
+    write files that compare element for element."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    g = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+
+    def sample(t, n):
+        idx = torch.randint(0, t.numel(), (n,), generator=g).sort().values
+        return t.reshape(-1)[idx.to(t.device)].cpu()
+
+    np.save(os.path.join(path, "out.npy"), sample(out, DUMP_OUT_SAMPLE).float().numpy())
+    # (the fp8 codes travel as bytes and are widened on the host)
+    np.save(os.path.join(path, "q.npy"), sample(q.view(torch.uint8), DUMP_Q_SAMPLE).view(FP8).float().numpy())
+    np.save(os.path.join(path, "s.npy"), s.float().cpu().contiguous().numpy())
 
 
 def pmc_traffic_bytes():
@@ -828,8 +859,13 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg next to the headline figure: %d repetitions of the timed region, MFMA ceilings, "
+                         "in-kernel clock, flash_mla_decode roofline, the extra legs, the CPU baseline" % REPS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave the extra legs out")
     # test hook (tests/test_bench_plumbing.py, CPU, gloo): rank / barrier / max-over-ranks / JSON plumbing with an
     # empty step; measures nothing and says so in the line it prints
     ap.add_argument("--plumbing-only", action="store_true", help=argparse.SUPPRESS)
@@ -867,12 +903,14 @@ def main(argv=None):
     # The part ramps its shader clock over the first tens of milliseconds of load (MI355X_MICROARCH.md, DVFS): W = 5
     # warm-up steps are 1.5 ms of work. Bring the chip to its steady state first with an untimed run of the same step
     # (reported in config.clock_ramp_ms), then do the W warm-up steps and the K timed steps as the contract says.
-    # The timed region is repeated REPS times (the devices of this pool differ by ~10 % and a single 20-step sample cannot show
-    # a 5 % kernel gain): every repetition is ramp + W warm-up steps + EXACTLY K timed steps between barrier + synchronize;
-    # `value` / `ms_per_step` / `roofline.achieved` are the MEDIAN repetition's, all of them are listed in `repetitions`.
+    # A plain run times the region once: ramp + W warm-up steps + EXACTLY K timed steps between barrier + synchronize.
+    # --full repeats it REPS times (devices differ by ~10 % and a single 20-step sample cannot show a 5 % kernel gain):
+    # `value` / `ms_per_step` / `roofline.achieved` are then the MEDIAN repetition's, all of them are listed in `repetitions`.
     flop = 2.0 * M * N * K
+    n_reps = REPS if args.full else 1
     reps = []
-    for _ in range(REPS):
+    last_out = [None]  # the GEMM result of the last timed step (--dump-outputs)
+    for _ in range(n_reps):
         ramp_t0 = time.perf_counter()
         while time.perf_counter() - ramp_t0 < CLOCK_RAMP_S:
             for _ in range(50):
@@ -888,22 +926,29 @@ def main(argv=None):
         def step(i):
             quant()
             ev[i][0].record()  # current stream == the stream the ops launch on
-            gemm()
+            out = gemm()
             ev[i][1].record()
+            if args.dump_outputs and i == args.steps - 1:
+                last_out[0] = out
 
         elapsed = timed_steps(step, args.steps, torch.cuda.synchronize, dist, dev)
         kms = sorted(a.elapsed_time(b_) for a, b_ in ev)
         reps.append({"ms_per_step": elapsed * 1e3 / args.steps, "kernel_ms_avg": sum(kms) / len(kms),
                      "kernel_ms_median": kms[len(kms) // 2], "kernel_ms_min": kms[0]})
-    order = sorted(range(REPS), key=lambda r: reps[r]["ms_per_step"])
-    med = reps[order[REPS // 2]]
+    order = sorted(range(n_reps), key=lambda r: reps[r]["ms_per_step"])
+    med = reps[order[n_reps // 2]]
     ms_per_step = med["ms_per_step"]
-    gemm_avg_ms = sorted(r["kernel_ms_avg"] for r in reps)[REPS // 2]
-    gemm_med_ms = sorted(r["kernel_ms_median"] for r in reps)[REPS // 2]
+    gemm_avg_ms = sorted(r["kernel_ms_avg"] for r in reps)[n_reps // 2]
+    gemm_med_ms = sorted(r["kernel_ms_median"] for r in reps)[n_reps // 2]
     gemm_min_ms = min(r["kernel_ms_min"] for r in reps)
 
-    clock = gemm_clock(q, b, s, sb, dev) if rank == 0 else None
-    ceiling = mfma_ceiling(dev) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        # q and s still hold what the last timed step's quant pass wrote: nothing has run since
+        dump_outputs(args.dump_outputs, last_out[0], q, s)
+    last_out[0] = None
+
+    clock = gemm_clock(q, b, s, sb, dev) if rank == 0 and args.full else None
+    ceiling = mfma_ceiling(dev) if rank == 0 and args.full else None
 
     value = world * flop / (ms_per_step * 1e-3) / 1e12
     achieved = flop / (gemm_avg_ms * 1e-3) / 1e12
@@ -926,7 +971,8 @@ def main(argv=None):
                         "(M=4096, N=14336, K=4096, 1x128 / 128x128 fp32 block scales, bf16 out)",
             "M": M, "N": N, "K": K, "parallelism": "replicas" if world > 1 else "single",
             "clock_ramp_ms": int(CLOCK_RAMP_S * 1e3),
-            "repetitions": REPS,
+            "repetitions": n_reps,
+            "full": args.full,
         },
         "repetitions": [{k: round(v, 4) for k, v in r.items()} | {"tflops": round(world * flop / r["ms_per_step"] / 1e9, 1)}
                         for r in reps],
@@ -958,7 +1004,7 @@ def main(argv=None):
         },
     }
     if rank == 0:
-        if world == 1:
+        if world == 1 and args.full:
             del x, b, sb, q, s
             # the "GB/s (flash decode)" half of the metric: its own roofline entry, measured in the same run
             fd = mla_roofline(sgl_kernel, dev)
@@ -974,10 +1020,10 @@ def main(argv=None):
             result["roofline"]["flash_decode_ms"] = fd["kernel_ms_avg"]
             result["roofline"]["bf16_ceiling_tflops_1_wave_per_simd"] = c4
             result["roofline"]["bf16_ceiling_tflops_2_waves_per_simd"] = c8
-        if world == 1 and not args.no_extra:
+        if world == 1 and args.full and not args.no_extra:
             result["extra"] = side_metrics(sgl_kernel, dev)
             result["roofline_extra"] = roofline_extra(result["extra"], result["roofline"].get("bf16_ceiling_tflops_2_waves_per_simd"))
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline()
         print(json.dumps(result), flush=True)
     if dist is not None:

@@ -48,6 +48,39 @@ def test_launcher_environment_is_used():
     assert json_lines[1] == []  # only rank 0 reports
 
 
+def test_full_and_dump_outputs_are_options(tmp_path):
+    """--full and --dump-outputs parse next to the contract's arguments (no kernel runs here, so nothing is written)"""
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "0", "--full", "--dump-outputs",
+                        str(tmp_path / "dump"), "--plumbing-only"], env=_clean_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])["steps"] == 2
+
+
+def test_dump_outputs_is_float32_seeded_and_bounded(tmp_path):
+    """dump_outputs on small host tensors: float32 files, the same bytes from call to call, every sampled value one of the
+    tensor's own, the scales complete; at the benchmark's shape the three files stay under 64 MB."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    assert 4 * (bench.DUMP_OUT_SAMPLE + bench.DUMP_Q_SAMPLE + bench.M * bench.K // bench.GROUP) <= 64 * 10 ** 6
+    g = torch.Generator().manual_seed(5)
+    out = torch.randn(37, 53, generator=g).to(torch.bfloat16)
+    q = (torch.randn(37, 256, generator=g) * 100).clamp(-448, 448).to(bench.FP8)
+    s = torch.rand(2, 37, generator=g).t()  # column-major, as the benchmark's
+    bench.dump_outputs(str(tmp_path / "a"), out, q, s)
+    bench.dump_outputs(str(tmp_path / "b"), out, q, s)
+    for name, src, n in (("out", out, bench.DUMP_OUT_SAMPLE), ("q", q, bench.DUMP_Q_SAMPLE)):
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (n,)
+        assert a.tobytes() == b.tobytes()
+        assert np.isin(a, src.float().numpy()).all()
+        assert set(np.unique(a)) == set(np.unique(src.float().numpy()))  # (n >> numel: every element is drawn)
+    sa = np.load(tmp_path / "a" / "s.npy")
+    assert sa.dtype == np.float32 and np.array_equal(sa, s.numpy())
+
+
 def test_gpus_must_match_world_size():
     env = dict(_clean_env(), RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     p = subprocess.run([sys.executable, BENCH, "--gpus", "4", "--plumbing-only"], env=env, capture_output=True, text=True, timeout=120)

@@ -17,7 +17,7 @@ mkdir -p $R/gpurun_out/r05
 SETS=${1:-"bench mla qserve attn prefill_128 prefill_64 prefill_chunk prefill_softcap"}
 for s in $SETS; do
   case $s in
-    bench) PROF_MEM=1 tools/gpu_prof.sh bench python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extra ;;
+    bench) PROF_MEM=1 tools/gpu_prof.sh bench python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extra ;;
     mla) MLA_GAUSS=100 PROF_MEM=1 tools/gpu_prof.sh mla $R/sgl-kernel-xpu_amd/build/kbench mla 128 8192 128 ;;
     qserve) PROF_MEM=1 tools/gpu_prof.sh qserve python3 $R/tools/qserve_bench.py 1 16 64 ;;
     attn) PROF_MEM=1 tools/gpu_prof.sh attn python3 $R/tools/attn_decode_sweep.py ;;
