@@ -382,6 +382,28 @@ SGLK_API int sglk_apply_shuffle_mul_sum_splitk(sglk_stream_t stream, const void*
                                                int64_t tokens, int64_t topk, int64_t hidden,
                                                float routed_scaling_factor, int dtype, int factors_dtype);
 
+/* ---- fp8 block-scaled grouped GEMM (MoE experts in the DeepSeek-V3 / Qwen3 fp8 checkpoint format) ---------------
+ * fp8_blockwise_scaled_grouped_mm: declared (never implemented) in reference include/sgl_kernel_ops.h:660-678; wrapper
+ * python/sgl_kernel/moe.py:236-275; semantics pinned by tests/test_fp8_blockwise_moe.py. For every expert e and its rows
+ * r in [expert_offsets[e], expert_offsets[e] + problem_sizes[3 e]):
+ *   out[r,n] = T( sum_kb sa[r,kb] * sb[e,kb,n/128] * sum_{k in kb} a[r,k]*b[e,k,n] )
+ * a [total_m, K] e4m3 row-major (lda); b [E, K, N] given K-contiguous, i.e. as [E, N, K] (expert stride b_stride_e, row
+ * stride ldb); sa [total_m, K/128] fp32 with element strides (sa_stride_m, sa_stride_k); sb [E, K/128, N/128] fp32
+ * (sb_stride_e, sb_stride_k, sb_stride_n); out [total_m, N] row-major (ldc), BF16 or F16. problem_sizes is the int32
+ * [E, 3] (m, n, k) list of the CUTLASS-style interface: only its m column is read; expert_offsets int32 [E]. Both are
+ * read on the device: no host sync, no allocation, no atomics, capturable into a graph. Counts of 0 are legal; rows
+ * of out that belong to no expert are not written; an expert's rows that leave [0, total_m) are ignored.
+ * K % 128 == 0 and N % 128 == 0 (anything else: SGLK_EUNSUPPORTED); a and b 16-byte aligned, lda, ldb and
+ * b_stride_e multiples of 16; 128 lda + K, 256 ldb + K and the scales of 128 rows below 2 GiB.
+ * total_m == 0 launches nothing. */
+SGLK_API int sglk_moe_fp8_blockwise_grouped_mm(sglk_stream_t stream, void* out, const void* a, const void* b,
+                                               const float* sa, const float* sb, const int32_t* problem_sizes,
+                                               const int32_t* expert_offsets, int64_t total_m, int64_t n_experts,
+                                               int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t b_stride_e,
+                                               int64_t ldc, int64_t sa_stride_m, int64_t sa_stride_k,
+                                               int64_t sb_stride_e, int64_t sb_stride_k, int64_t sb_stride_n,
+                                               int out_dtype);
+
 /* ---- flash-attention forward ---------------------------------------------------
  * fwd (mha_fwd): reference src/sycl/flash_attention.cpp:1332-1435 (schema
  * src/torch_extension_sycl.cc:328-358; wrappers python/sgl_kernel/flash_attn.py:103-372).

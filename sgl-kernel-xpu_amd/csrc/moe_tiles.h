@@ -92,6 +92,60 @@ __device__ __forceinline__ MoeTile find_moe_tile(const int32_t* __restrict__ row
   return t;
 }
 
+// Sibling of find_moe_tile for callers that pass the experts' first rows explicitly (moe_fp8bw.hip: expert_offsets next to
+// the [E, 3] problem_sizes of the CUTLASS-style grouped GEMM interface): rows of expert e = counts[e * count_stride] rows
+// from starts[e]. Rows between two experts belong to nobody. A (start, count) pair that leaves [0, total_rows) is cut to
+// what lies inside, so that no tile ever names a row the caller did not allocate. Row blocks fastest, no tail mode.
+__device__ __forceinline__ MoeTile find_moe_tile_at(const int32_t* __restrict__ counts, int count_stride,
+                                                    const int32_t* __restrict__ starts, int E, int total_rows, int BM,
+                                                    int NB) {
+  const int lane = threadIdx.x & 63;
+  auto rows_of = [&](int e, int& start) -> int {
+    if (e >= E) return start = 0;
+    start = starts[e];
+    const int r = counts[(int64_t)e * count_stride];
+    if (start < 0 || start >= total_rows || r <= 0) return 0;
+    return r < total_rows - start ? r : total_rows - start;
+  };
+  int MB = 0;
+  for (int c0 = 0; c0 < E; c0 += 64) {
+    int s;
+    const int r = rows_of(c0 + lane, s);
+    MB += __shfl(wave_inclusive_scan((r + BM - 1) / BM, lane), 63, 64);
+  }
+  MB = __builtin_amdgcn_readfirstlane(MB);
+  MoeTile t = {-1, 0, 0, 0};
+  const int real = MB * NB, real8 = real & ~7;
+  int L = blockIdx.x;
+  if (L >= real) return t;
+  if (L < real8) L = (L & 7) * (real8 >> 3) + (L >> 3);  // (XCD x takes a contiguous eighth of the real tiles, as above)
+  const int mblk = L % MB;
+  int e = 0, row0 = 0, rows_e = 0, blk = 0, base_b = 0;
+  for (int c0 = 0; c0 < E; c0 += 64) {
+    int s;
+    const int r = rows_of(c0 + lane, s);
+    const int nb = (r + BM - 1) / BM;
+    const int ib = wave_inclusive_scan(nb, lane);
+    const bool hit = mblk >= base_b + ib - nb && mblk < base_b + ib;
+    const unsigned long long m = __ballot(hit);
+    if (m != 0) {
+      const int src = __builtin_ctzll(m);
+      e = c0 + src;
+      blk = mblk - (base_b + __shfl(ib - nb, src, 64));
+      row0 = __shfl(s, src, 64);
+      rows_e = __shfl(r, src, 64);
+      break;
+    }
+    base_b += __shfl(ib, 63, 64);
+  }
+  t.expert = __builtin_amdgcn_readfirstlane(e);
+  blk = __builtin_amdgcn_readfirstlane(blk);
+  t.m0 = __builtin_amdgcn_readfirstlane(row0) + blk * BM;
+  t.m_valid = __builtin_amdgcn_readfirstlane(rows_e) - blk * BM;
+  t.col_block = L / MB;
+  return t;
+}
+
 // launch size for find_moe_tile
 inline int64_t moe_tile_launch_size(int64_t total_rows, int64_t E, int64_t BM, int64_t NB) {
   return ((total_rows / BM + E) * NB + 7) / 8 * 8;

@@ -281,6 +281,55 @@ Tensor fp8_blockwise_scaled_mm(const Tensor& mat_a, const Tensor& mat_b, const T
   return out;
 }
 
+// ---- fp8 blockwise grouped GEMM (declared only: reference include/sgl_kernel_ops.h:660-678) ----------
+// a_ptrs .. b_scales_ptrs, stride_a / b / c, layout_sfa / sfb and workspace are scratch of the CUTLASS implementation
+// the interface was written for (per-expert pointer, stride and scale-layout arrays a setup kernel fills). They are
+// accepted and checked to live on the device, and neither read nor written: this kernel addresses the experts from
+// problem_sizes and expert_offsets alone, and reading anything of them on the host would cost a sync.
+
+void fp8_blockwise_scaled_grouped_mm(Tensor& output, Tensor& a_ptrs, Tensor& b_ptrs, Tensor& out_ptrs,
+                                     Tensor& a_scales_ptrs, Tensor& b_scales_ptrs, const Tensor& a, const Tensor& b,
+                                     const Tensor& scales_a, const Tensor& scales_b, const Tensor& stride_a,
+                                     const Tensor& stride_b, const Tensor& stride_c, const Tensor& layout_sfa,
+                                     const Tensor& layout_sfb, const Tensor& problem_sizes,
+                                     const Tensor& expert_offsets, const Tensor& workspace) {
+  for (const Tensor* t : std::initializer_list<const Tensor*>{
+           &output, &a_ptrs, &b_ptrs, &out_ptrs, &a_scales_ptrs, &b_scales_ptrs, &a, &b, &scales_a, &scales_b, &stride_a,
+           &stride_b, &stride_c, &layout_sfa, &layout_sfb, &problem_sizes, &expert_offsets, &workspace})
+    TORCH_CHECK(t->is_cuda(), "fp8_blockwise_scaled_grouped_mm: all tensors must be GPU (cuda/hip) tensors");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 3, "a must be [total_m, K] and b [E, K, N]");
+  TORCH_CHECK(a.scalar_type() == at::kFloat8_e4m3fn, "a must be Float8_e4m3fn");
+  TORCH_CHECK(b.scalar_type() == at::kFloat8_e4m3fn, "b must be Float8_e4m3fn");
+  TORCH_CHECK(a.stride(1) == 1, "a must be row major");
+  TORCH_CHECK(b.stride(1) == 1, "b must be [E, K, N] with K contiguous (the transposed view of [E, N, K])");
+  TORCH_CHECK(scales_a.scalar_type() == at::kFloat && scales_b.scalar_type() == at::kFloat,
+              "scales_a and scales_b must be Float32");
+  const int64_t total_m = a.size(0), K = a.size(1), E = b.size(0), N = b.size(2);
+  TORCH_CHECK(b.size(1) == K, "a and b disagree on K");
+  TORCH_CHECK(K % 128 == 0 && N % 128 == 0, "K and N must be multiples of 128 (one scale per 128-deep / 128-wide block)");
+  TORCH_CHECK(scales_a.dim() == 2 && scales_a.size(0) == total_m && scales_a.size(1) == K / 128,
+              "scales_a must have shape [total_m, K/128]");
+  TORCH_CHECK(scales_b.dim() == 3 && scales_b.size(0) == E && scales_b.size(1) == K / 128 && scales_b.size(2) == N / 128,
+              "scales_b must have shape [E, K/128, N/128]");
+  TORCH_CHECK(problem_sizes.scalar_type() == at::kInt && problem_sizes.dim() == 2 && problem_sizes.size(0) == E &&
+                  problem_sizes.size(1) == 3 && problem_sizes.is_contiguous(),
+              "problem_sizes must be a contiguous Int32 [E, 3] tensor");
+  TORCH_CHECK(expert_offsets.scalar_type() == at::kInt && expert_offsets.dim() == 1 && expert_offsets.size(0) == E &&
+                  expert_offsets.stride(0) == 1,
+              "expert_offsets must be an Int32 tensor with E entries");
+  const auto out_t = output.scalar_type();
+  TORCH_CHECK(out_t == at::kHalf || out_t == at::kBFloat16, "output must be Half or BFloat16");
+  TORCH_CHECK(output.dim() == 2 && output.size(0) == total_m && output.size(1) == N && (output.stride(1) == 1 || N == 1),
+              "output must be [total_m, N] with a contiguous last dimension");
+  if (total_m == 0) return;
+  const c10::OptionalDeviceGuard guard(a.device());
+  SGLK_CALL(sglk_moe_fp8_blockwise_grouped_mm(
+      stream_of(a), output.data_ptr(), a.data_ptr(), b.data_ptr(), scales_a.data_ptr<float>(), scales_b.data_ptr<float>(),
+      problem_sizes.data_ptr<int32_t>(), expert_offsets.data_ptr<int32_t>(), total_m, E, N, K, a.stride(0), b.stride(2),
+      b.stride(0), output.stride(0), scales_a.stride(0), scales_a.stride(1), scales_b.stride(0), scales_b.stride(1),
+      scales_b.stride(2), dtype_code(out_t, "output")));
+}
+
 // ---- fp8 / int8 per-token x per-channel GEMM (declared only: reference
 // include/sgl_kernel_ops.h:567-580; call order python/sgl_kernel/gemm.py:13-42) -----------------
 
@@ -1711,6 +1760,13 @@ TORCH_LIBRARY_FRAGMENT(sgl_kernel, m) {
       "fp8_blockwise_scaled_mm(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype)"
       " -> Tensor");
   m.impl("fp8_blockwise_scaled_mm", c10::kCUDA, &fp8_blockwise_scaled_mm);
+  // authored: reference include/sgl_kernel_ops.h:660-678 + python/sgl_kernel/moe.py:236-275
+  m.def(
+      "fp8_blockwise_scaled_grouped_mm(Tensor! output, Tensor! a_ptrs, Tensor! b_ptrs, Tensor! out_ptrs,"
+      " Tensor! a_scales_ptrs, Tensor! b_scales_ptrs, Tensor a, Tensor b, Tensor scales_a, Tensor scales_b,"
+      " Tensor stride_a, Tensor stride_b, Tensor stride_c, Tensor layout_sfa, Tensor layout_sfb,"
+      " Tensor problem_sizes, Tensor expert_offsets, Tensor workspace) -> ()");
+  m.impl("fp8_blockwise_scaled_grouped_mm", c10::kCUDA, &fp8_blockwise_scaled_grouped_mm);
   // authored: reference include/sgl_kernel_ops.h:567-580 + python/sgl_kernel/gemm.py:13-42
   m.def(
       "fp8_scaled_mm(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype,"

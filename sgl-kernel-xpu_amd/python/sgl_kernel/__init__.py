@@ -58,6 +58,7 @@ from sgl_kernel.gemm import (  # noqa: E402
 from sgl_kernel.moe import (  # noqa: E402
     apply_shuffle_mul_sum,
     biased_topk,
+    fp8_blockwise_scaled_grouped_mm,
     fused_experts,
     swiglu_gpt_oss_sigmoid_alpha,
     moe_align_block_size,
@@ -93,7 +94,7 @@ _OUT_OF_SCOPE = frozenset(
     embedding_lora_a_fwd fast_topk_transform_fused fast_topk_transform_ragged_fused fast_topk_v2
     flash_compress128_decode flash_compress128_prefill flash_compress4_decode
     flash_compress4_prefill flash_mla_sparse_fwd flash_mla_with_kvcache
-    fp8_blockwise_scaled_grouped_mm fp8_mqa_logits fp8_paged_mqa_logits
+    fp8_mqa_logits fp8_paged_mqa_logits
     fp8_paged_mqa_logits_triton fused_causal_conv1d_update_decode fused_decode_sconv_metadata
     fused_draft_extend_sconv_cache fused_extend_sconv_metadata
     fused_gather_scatter_to_sconv_cache fused_k_norm_rope_flashmla

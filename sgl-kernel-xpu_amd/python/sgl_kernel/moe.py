@@ -96,6 +96,18 @@ def scatter_tokens_to_experts(input, src2dst_map, output):
     _ops.scatter_tokens_to_experts.default(input, src2dst_map, output)
 
 
+def fp8_blockwise_scaled_grouped_mm(output, a_ptrs, b_ptrs, out_ptrs, a_scales_ptrs, b_scales_ptrs, a, b, scales_a, scales_b,
+                                    stride_a, stride_b, stride_c, layout_sfa, layout_sfb, problem_sizes, expert_offsets,
+                                    workspace):
+    """Block-scaled fp8 grouped GEMM over the experts' row lists (reference moe.py:236-275): for expert e and its rows
+    r in [expert_offsets[e], expert_offsets[e] + problem_sizes[e, 0]), output[r] = (scales_a (x) a)[r] @ (scales_b (x) b)[e].
+    a [total_m, K] e4m3, b [E, K, N] e4m3 with K contiguous, scales_a [total_m, K/128], scales_b [E, K/128, N/128] fp32 (any
+    strides). The pointer, stride, layout and workspace tensors are scratch of the CUTLASS implementation: accepted, untouched."""
+    _ops.fp8_blockwise_scaled_grouped_mm.default(output, a_ptrs, b_ptrs, out_ptrs, a_scales_ptrs, b_scales_ptrs, a, b, scales_a,
+                                                 scales_b, stride_a, stride_b, stride_c, layout_sfa, layout_sfb, problem_sizes,
+                                                 expert_offsets, workspace)
+
+
 # ------------------------------------------------------------------------------------------------ scratch
 
 class _Scratch:
