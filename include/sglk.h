@@ -404,6 +404,39 @@ SGLK_API int sglk_moe_fp8_blockwise_grouped_mm(sglk_stream_t stream, void* out, 
                                                int64_t sb_stride_e, int64_t sb_stride_k, int64_t sb_stride_n,
                                                int out_dtype);
 
+/* ---- fp8 MQA logits (the DeepSeek-V3.2 sparse-attention indexer) ------------------------------------------------
+ * fp8_mqa_logits / fp8_paged_mqa_logits: reference python/sgl_kernel/nsa.py:112-185 (schema
+ * src/torch_extension_sycl.cc), fp8_paged_mqa_logits_triton: python/sgl_kernel/fp8_paged_mqa_logits.py:82.
+ *   logits[i,j] = k_scale[j] * sum_h weights[i,h] * relu(q[i,h,:] . k[j,:])   for j inside the window of query i, else 0
+ * q [n_q or batch, heads, 128] e4m3 bytes, contiguous, 16-byte aligned; weights [.., heads] fp32, contiguous, signed;
+ * logits fp32 with row stride ld_logits (elements). heads 1..64 and head_dim 128, anything else: SGLK_EUNSUPPORTED.
+ * Both are pure functions of their inputs: no host sync, no allocation, no atomics, capturable into a graph; EVERY
+ * element of logits[0..n_q, 0..n_k) / logits[0..batch, 0..max_seq_len) is written (zeros outside the window; the
+ * reference writes zeros there too, not -inf), columns past that up to ld_logits are not touched.
+ *
+ * sglk_fp8_mqa_logits (ragged / prefill): k [n_k, 128] e4m3 bytes, contiguous, 16-byte aligned; k_scale [n_k] fp32;
+ * the window of query i is [ks[i], ke[i]) (int32, clamped to [0, n_k]; ke <= ks: an empty row). n_k < 2^24,
+ * 16 * ld_logits * 4 < 2^31, n_q < 2^20. n_q == 0 or n_k == 0 launches nothing.
+ *
+ * sglk_fp8_paged_mqa_logits (decode): one query per sequence, window [0, seq_lens[b]) (int32, clamped to
+ * [0, max_seq_len]). kv_cache is num_pages pages of page_size * 132 bytes, 4-byte aligned, in one of two layouts:
+ *   SGLK_MQA_CACHE_ROWS   token t of page p at byte (p * page_size + t) * 132: 128 key bytes, then its fp32 scale
+ *   SGLK_MQA_CACHE_BLOCKS inside page p (at byte p * page_size * 132) first page_size * 128 key bytes, then page_size
+ *                         fp32 scales
+ * Key j of sequence b lives in page block_tables[b * table_stride + j / page_size] (int32), slot j % page_size. Any
+ * page_size in [1, 2^20). Entries at or past ceil(seq_lens[b] / page_size) are never read; entries that are read are
+ * clamped to [0, num_pages - 1], so a bad entry gives wrong numbers and never a fault. table_stride >=
+ * ceil(max_seq_len / page_size). batch == 0 or max_seq_len == 0 launches nothing; batch < 65536. */
+enum sglk_mqa_cache_layout { SGLK_MQA_CACHE_ROWS = 0, SGLK_MQA_CACHE_BLOCKS = 1 };
+SGLK_API int sglk_fp8_mqa_logits(sglk_stream_t stream, float* logits, const void* q, const void* k, const float* k_scale,
+                                 const float* weights, const int32_t* ks, const int32_t* ke, int64_t n_q, int64_t n_k,
+                                 int64_t heads, int64_t head_dim, int64_t ld_logits);
+SGLK_API int sglk_fp8_paged_mqa_logits(sglk_stream_t stream, float* logits, const void* q, const void* kv_cache,
+                                       const float* weights, const int32_t* seq_lens, const int32_t* block_tables,
+                                       int64_t batch, int64_t heads, int64_t head_dim, int64_t page_size,
+                                       int64_t num_pages, int64_t table_stride, int64_t max_seq_len, int64_t ld_logits,
+                                       int layout);
+
 /* ---- flash-attention forward ---------------------------------------------------
  * fwd (mha_fwd): reference src/sycl/flash_attention.cpp:1332-1435 (schema
  * src/torch_extension_sycl.cc:328-358; wrappers python/sgl_kernel/flash_attn.py:103-372).

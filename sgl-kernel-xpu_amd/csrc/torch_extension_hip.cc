@@ -330,6 +330,76 @@ void fp8_blockwise_scaled_grouped_mm(Tensor& output, Tensor& a_ptrs, Tensor& b_p
       scales_b.stride(2), dtype_code(out_t, "output")));
 }
 
+// ---- fp8 MQA logits of the DeepSeek-V3.2 indexer (reference python/sgl_kernel/nsa.py:112-185,
+// fp8_paged_mqa_logits.py:82; kernels: csrc/mqa_logits.hip) ------------------------------------------------------
+
+static void check_fp8_bytes(const Tensor& t, const char* op, const char* name) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be a GPU (cuda/hip) tensor");
+  TORCH_CHECK(t.scalar_type() == at::kByte || t.scalar_type() == at::kFloat8_e4m3fn, op, ": ", name,
+              " must be uint8 or Float8_e4m3fn");
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+Tensor fp8_mqa_logits(const Tensor& q_fp8, const Tensor& k_fp8, const Tensor& k_scale, const Tensor& weights, const Tensor& ks,
+                      const Tensor& ke) {
+  const char* op = "fp8_mqa_logits";
+  check_fp8_bytes(q_fp8, op, "q_fp8");
+  check_fp8_bytes(k_fp8, op, "k_fp8");
+  TORCH_CHECK(q_fp8.dim() == 3 && k_fp8.dim() == 2 && q_fp8.size(2) == k_fp8.size(1), op,
+              ": q_fp8 must be [Nq, H, D] and k_fp8 [Nk, D]");
+  const int64_t Nq = q_fp8.size(0), H = q_fp8.size(1), Dh = q_fp8.size(2), Nk = k_fp8.size(0);
+  TORCH_CHECK(Dh == 128 && H >= 1 && H <= 64, op, ": head_dim must be 128 and heads at most 64");
+  for (const Tensor* t : {&k_scale, &weights, &ks, &ke}) TORCH_CHECK(t->is_cuda() && t->is_contiguous(), op, ": all tensors must be contiguous GPU tensors");
+  TORCH_CHECK(k_scale.scalar_type() == at::kFloat && k_scale.numel() == Nk, op, ": k_scale must be Float32 with Nk elements");
+  TORCH_CHECK(weights.scalar_type() == at::kFloat && weights.dim() == 2 && weights.size(0) == Nq && weights.size(1) == H, op,
+              ": weights must be Float32 [Nq, H]");
+  TORCH_CHECK(ks.scalar_type() == at::kInt && ke.scalar_type() == at::kInt && ks.numel() == Nq && ke.numel() == Nq, op,
+              ": ks and ke must be Int32 with Nq elements");
+  Tensor logits = at::empty({Nq, Nk}, weights.options());
+  if (Nq == 0 || Nk == 0) return logits;
+  const c10::OptionalDeviceGuard guard(q_fp8.device());
+  SGLK_CALL(sglk_fp8_mqa_logits(stream_of(q_fp8), logits.data_ptr<float>(), q_fp8.data_ptr(), k_fp8.data_ptr(),
+                                k_scale.data_ptr<float>(), weights.data_ptr<float>(), ks.data_ptr<int32_t>(),
+                                ke.data_ptr<int32_t>(), Nq, Nk, H, Dh, logits.stride(0)));
+  return logits;
+}
+
+// schedule_metadata and clean_logits belong to the reference's schema: accepted and ignored (every element of the result is
+// written, zeros outside [0, seq_len)). block_layout selects the cache layout (include/sglk.h).
+Tensor fp8_paged_mqa_logits(const Tensor& q_fp8, const Tensor& kv_cache, const Tensor& weights, const Tensor& seq_lens,
+                            const Tensor& block_tables, const std::optional<Tensor>& schedule_metadata, int64_t max_seq_len,
+                            bool clean_logits, bool block_layout) {
+  const char* op = "fp8_paged_mqa_logits";
+  check_fp8_bytes(q_fp8, op, "q_fp8");
+  check_fp8_bytes(kv_cache, op, "kv_cache");
+  TORCH_CHECK(q_fp8.dim() == 4 && q_fp8.size(1) == 1, op, ": q_fp8 must be [B, 1, H, D]");
+  const int64_t B = q_fp8.size(0), H = q_fp8.size(2), Dh = q_fp8.size(3);
+  TORCH_CHECK(Dh == 128 && H >= 1 && H <= 64, op, ": head_dim must be 128 and heads at most 64");
+  TORCH_CHECK(kv_cache.dim() >= 2 && kv_cache.size(-1) == Dh + 4 && kv_cache.numel() == kv_cache.size(0) * kv_cache.size(1) * (Dh + 4),
+              op, ": kv_cache must be [num_pages, page_size, 1, D + 4]");
+  const int64_t num_pages = kv_cache.size(0), page_size = kv_cache.size(1);
+  for (const Tensor* t : {&weights, &seq_lens, &block_tables}) TORCH_CHECK(t->is_cuda(), op, ": all tensors must be GPU tensors");
+  TORCH_CHECK(weights.scalar_type() == at::kFloat && weights.is_contiguous() && weights.dim() == 2 && weights.size(0) == B &&
+                  weights.size(1) == H, op, ": weights must be a contiguous Float32 [B, H]");
+  TORCH_CHECK(seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous() && seq_lens.numel() == B, op,
+              ": seq_lens must be a contiguous Int32 tensor with B elements");
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt && block_tables.dim() == 2 && block_tables.size(0) == B &&
+                  (block_tables.stride(1) == 1 || block_tables.size(1) <= 1), op, ": block_tables must be Int32 [B, max_blocks]");
+  TORCH_CHECK(max_seq_len >= 0 && (num_pages > 0 || B == 0 || max_seq_len == 0), op, ": bad max_seq_len or an empty cache");
+  TORCH_CHECK(page_size > 0 && block_tables.size(1) * page_size >= max_seq_len, op,
+              ": block_tables has fewer than ceil(max_seq_len / page_size) columns");
+  Tensor logits = at::empty({B, max_seq_len}, weights.options());
+  if (B == 0 || max_seq_len == 0) return logits;
+  const c10::OptionalDeviceGuard guard(q_fp8.device());
+  // (a one-row table may carry any stride: the kernel needs one that covers its columns)
+  const int64_t table_stride = B > 1 ? block_tables.stride(0) : block_tables.size(1);
+  SGLK_CALL(sglk_fp8_paged_mqa_logits(stream_of(q_fp8), logits.data_ptr<float>(), q_fp8.data_ptr(), kv_cache.data_ptr(),
+                                      weights.data_ptr<float>(), seq_lens.data_ptr<int32_t>(), block_tables.data_ptr<int32_t>(),
+                                      B, H, Dh, page_size, num_pages, table_stride, max_seq_len, logits.stride(0),
+                                      block_layout ? SGLK_MQA_CACHE_BLOCKS : SGLK_MQA_CACHE_ROWS));
+  return logits;
+}
+
 // ---- fp8 / int8 per-token x per-channel GEMM (declared only: reference
 // include/sgl_kernel_ops.h:567-580; call order python/sgl_kernel/gemm.py:13-42) -----------------
 
@@ -1767,6 +1837,13 @@ TORCH_LIBRARY_FRAGMENT(sgl_kernel, m) {
       " Tensor stride_a, Tensor stride_b, Tensor stride_c, Tensor layout_sfa, Tensor layout_sfb,"
       " Tensor problem_sizes, Tensor expert_offsets, Tensor workspace) -> ()");
   m.impl("fp8_blockwise_scaled_grouped_mm", c10::kCUDA, &fp8_blockwise_scaled_grouped_mm);
+  // authored: reference python/sgl_kernel/nsa.py:112-185 (the paged schema is the reference's plus block_layout)
+  m.def("fp8_mqa_logits(Tensor q_fp8, Tensor k_fp8, Tensor k_scale, Tensor weights, Tensor ks, Tensor ke) -> Tensor");
+  m.impl("fp8_mqa_logits", c10::kCUDA, &fp8_mqa_logits);
+  m.def(
+      "fp8_paged_mqa_logits(Tensor q_fp8, Tensor kv_cache, Tensor weights, Tensor seq_lens, Tensor block_tables,"
+      " Tensor? schedule_metadata, int max_seq_len, bool clean_logits, bool block_layout=False) -> Tensor");
+  m.impl("fp8_paged_mqa_logits", c10::kCUDA, &fp8_paged_mqa_logits);
   // authored: reference include/sgl_kernel_ops.h:567-580 + python/sgl_kernel/gemm.py:13-42
   m.def(
       "fp8_scaled_mm(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype,"

@@ -68,6 +68,7 @@ from sgl_kernel.moe import (  # noqa: E402
     topk_sigmoid,
     topk_softmax,
 )
+from sgl_kernel.nsa import fp8_mqa_logits, fp8_paged_mqa_logits, fp8_paged_mqa_logits_triton  # noqa: E402
 from sgl_kernel.sampling import (  # noqa: E402
     min_p_sampling_from_probs,
     top_k_renorm_prob,
@@ -94,8 +95,7 @@ _OUT_OF_SCOPE = frozenset(
     embedding_lora_a_fwd fast_topk_transform_fused fast_topk_transform_ragged_fused fast_topk_v2
     flash_compress128_decode flash_compress128_prefill flash_compress4_decode
     flash_compress4_prefill flash_mla_sparse_fwd flash_mla_with_kvcache
-    fp8_mqa_logits fp8_paged_mqa_logits
-    fp8_paged_mqa_logits_triton fused_causal_conv1d_update_decode fused_decode_sconv_metadata
+    fused_causal_conv1d_update_decode fused_decode_sconv_metadata
     fused_draft_extend_sconv_cache fused_extend_sconv_metadata
     fused_gather_scatter_to_sconv_cache fused_k_norm_rope_flashmla
     fused_q_indexer_rope_hadamard_quant fused_q_norm_rope fused_qk_rope
