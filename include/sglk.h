@@ -437,6 +437,35 @@ SGLK_API int sglk_fp8_paged_mqa_logits(sglk_stream_t stream, float* logits, cons
                                        int64_t num_pages, int64_t table_stride, int64_t max_seq_len, int64_t ld_logits,
                                        int layout);
 
+/* ---- exact top-k selection behind the indexer scores ----------------------------------------------------------
+ * fast_topk_v2 / fast_topk_transform_fused / fast_topk_transform_ragged_fused / topk_transform_512 / _v2: reference
+ * src/sycl/TopKTransform.cpp, python/sgl_kernel/top_k.py. For every row b of score [rows, width] fp32 (row stride
+ * ld_score elements, 4-byte aligned) the topk largest elements of the window score[b, rs : rs + len] are selected,
+ * rs = row_starts[b] (0 if row_starts is null), len = lengths[b], and slot i of out[b, 0..topk) (int32, row stride
+ * ld_out) receives the selected window-relative index p mapped by `mode`:
+ *   SGLK_TOPK_RAW         p
+ *   SGLK_TOPK_PAGE_TABLE  table[s * ld_table + p]; s = b if aux is null, else the s with aux[s] <= b < aux[s + 1]
+ *                         (aux = cu_seqlens_q, table_rows + 1 non-decreasing entries, found by binary search)
+ *   SGLK_TOPK_OFFSET      p + aux[b]  (aux = topk_indices_offset, rows entries)
+ *   SGLK_TOPK_PAGED       (table[b * ld_table + (p >> log2 page_size)] << log2 page_size) | (p & (page_size - 1))
+ * out_raw (nullable, row stride ld_raw) receives p itself as well. The selection is EXACT for every input: the selected
+ * values are the topk largest, and among elements equal to the topk-th value the lowest indices are taken. Elements
+ * order by the key `bits ^ (bits < 0 ? ~0 : 0x80000000)`: -0.0 sorts below +0.0 and a positive NaN above +inf. The
+ * order of the slots is unspecified but a pure function of the inputs (no atomics on global memory, no free-running
+ * counters): the same bits on every run. len <= topk: slot i < len holds the mapping of i, every later slot -1;
+ * len <= 0: all -1.
+ * Limits: topk 1..2048 (else SGLK_EUNSUPPORTED), width < 2^28, page_size a power of two <= 2^20. Clamped: rs to
+ * [0, width], len to [0, width - rs], s to [0, table_rows - 1], the table column to [0, table_cols - 1] - a bad
+ * row_starts / lengths / cu_seqlens_q value or a table narrower than the window gives wrong numbers and never a fault.
+ * Never read: score outside the clamped window (columns width..ld_score included), table / aux in RAW mode, aux in
+ * PAGED mode. Without aux the table needs table_rows >= rows. No host sync, no allocation, capturable into a graph;
+ * rows == 0 launches nothing. One workgroup per row: a single very long row (batch-1 decode) is not split. */
+enum sglk_topk_mode { SGLK_TOPK_RAW = 0, SGLK_TOPK_PAGE_TABLE = 1, SGLK_TOPK_OFFSET = 2, SGLK_TOPK_PAGED = 3 };
+SGLK_API int sglk_topk_select(sglk_stream_t stream, int32_t* out, int32_t* out_raw, const float* score,
+                              const int32_t* lengths, const int32_t* row_starts, const int32_t* table, const int32_t* aux,
+                              int64_t rows, int64_t width, int64_t ld_score, int64_t topk, int64_t ld_out, int64_t ld_raw,
+                              int64_t table_rows, int64_t table_cols, int64_t ld_table, int64_t page_size, int mode);
+
 /* ---- flash-attention forward ---------------------------------------------------
  * fwd (mha_fwd): reference src/sycl/flash_attention.cpp:1332-1435 (schema
  * src/torch_extension_sycl.cc:328-358; wrappers python/sgl_kernel/flash_attn.py:103-372).

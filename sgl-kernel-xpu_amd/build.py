@@ -79,7 +79,7 @@ def run(cmd):
 
 # sources whose device assembly is kept next to the object (-save-temps=obj) for check_isa
 ISA_CHECKED = ("mla_decode.hip", "gemm_8bit.hip", "attn_fwd.hip", "moe_w4a16.hip", "moe_bf16.hip", "moe_persist.hip",
-               "moe_fp8bw.hip", "mqa_logits.hip")
+               "moe_fp8bw.hip", "mqa_logits.hip", "topk_select.hip")
 
 
 def _asm_path(src_name, obj_dir=None):
@@ -189,7 +189,9 @@ def check_isa(verbose=True):
                           # (moe_fp8bw counts its LDS-DMA by hand: scratch traffic in the K loop sits inside the counted window)
                           ("moe_fp8bw.hip", r"moe_fp8bw_tile_kernelI"),
                           # (mqa_ragged counts its LDS-DMA and its stores by hand; mqa_paged's register ring must stay in registers)
-                          ("mqa_logits.hip", r"mqa_ragged_kernelI"), ("mqa_logits.hip", r"mqa_paged_kernelI")):
+                          ("mqa_logits.hip", r"mqa_ragged_kernelI"), ("mqa_logits.hip", r"mqa_paged_kernelI"),
+                          # (topk_select is sized for 128 registers, two 512-thread workgroups a CU, with 4 loads in flight a lane)
+                          ("topk_select.hip", r"topk_select_kernelE")):
         path = _asm_path(src_name)
         if not os.path.exists(path):
             problems.append("%s missing" % path)

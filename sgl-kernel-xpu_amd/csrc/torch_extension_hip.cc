@@ -400,6 +400,90 @@ Tensor fp8_paged_mqa_logits(const Tensor& q_fp8, const Tensor& kv_cache, const T
   return logits;
 }
 
+// ---- exact top-k selection behind the indexer scores (reference src/sycl/TopKTransform.cpp, python/sgl_kernel/top_k.py;
+// kernel: csrc/topk_select.hip). One kernel, four epilogues (include/sglk.h). ------------------------------------------
+
+static void check_i32(const Tensor& t, const char* op, const char* name, int64_t numel) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(), op, ": ", name,
+              " must be a contiguous Int32 GPU tensor");
+  TORCH_CHECK(numel < 0 || t.numel() == numel, op, ": ", name, " must have ", numel, " elements, got ", t.numel());
+}
+
+// a 2-D int32 matrix whose rows are contiguous; returns the row stride the kernel may use
+static int64_t check_i32_rows(const Tensor& t, const char* op, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.dim() == 2, op, ": ", name, " must be a 2-D Int32 GPU tensor");
+  TORCH_CHECK(t.stride(1) == 1 || t.size(1) <= 1, op, ": the last dimension of ", name, " must be contiguous");
+  return t.size(0) > 1 ? t.stride(0) : t.size(1);
+}
+
+static void topk_select(const char* op, const Tensor& score, const Tensor& lengths, const std::optional<Tensor>& row_starts,
+                        Tensor& dst, const std::optional<Tensor>& raw, const Tensor* table, const Tensor* aux, int64_t aux_numel,
+                        int64_t topk, int64_t page_size, int mode) {
+  TORCH_CHECK(score.is_cuda() && score.scalar_type() == at::kFloat && score.dim() == 2, op, ": score must be a 2-D Float32 GPU tensor");
+  TORCH_CHECK(score.stride(1) == 1 || score.size(1) <= 1, op, ": the last dimension of score must be contiguous");
+  const int64_t B = score.size(0), L = score.size(1);
+  check_i32(lengths, op, "lengths", B);
+  if (row_starts) check_i32(*row_starts, op, "row_starts", B);
+  const int64_t ld_out = check_i32_rows(dst, op, "the output");
+  TORCH_CHECK(dst.size(0) == B && dst.size(1) == topk, op, ": the output must be [", B, ", ", topk, "]");
+  int64_t ld_raw = 0;
+  if (raw) {
+    ld_raw = check_i32_rows(*raw, op, "out_raw_indices");
+    TORCH_CHECK(raw->size(0) == B && raw->size(1) == topk, op, ": out_raw_indices must be [", B, ", ", topk, "]");
+  }
+  int64_t ld_table = 0;
+  if (table) {
+    ld_table = check_i32_rows(*table, op, "the page table");
+    TORCH_CHECK(B == 0 || (table->size(0) >= 1 && table->size(1) >= 1), op, ": the page table is empty");
+    TORCH_CHECK(aux || table->size(0) >= B, op, ": the page table has fewer rows than score");
+  }
+  if (aux) check_i32(*aux, op, mode == SGLK_TOPK_OFFSET ? "topk_indices_offset" : "cu_seqlens_q", aux_numel);
+  if (B == 0) return;
+  const c10::OptionalDeviceGuard guard(score.device());
+  SGLK_CALL(sglk_topk_select(stream_of(score), dst.data_ptr<int32_t>(), raw ? raw->data_ptr<int32_t>() : nullptr,
+                             score.data_ptr<float>(), lengths.data_ptr<int32_t>(),
+                             row_starts ? row_starts->data_ptr<int32_t>() : nullptr, table ? table->data_ptr<int32_t>() : nullptr,
+                             aux ? aux->data_ptr<int32_t>() : nullptr, B, L, B > 1 ? score.stride(0) : L, topk, ld_out, ld_raw,
+                             table ? table->size(0) : 0, table ? table->size(1) : 0, ld_table, page_size, mode));
+}
+
+void fast_topk(const Tensor& score, Tensor& indices, const Tensor& lengths, const std::optional<Tensor>& row_starts) {
+  topk_select("fast_topk", score, lengths, row_starts, indices, std::nullopt, nullptr, nullptr, 0, 2048, 1, SGLK_TOPK_RAW);
+}
+
+// decode form (no row_starts, a table row per score row): row b reads table row b; otherwise the row's sequence is
+// looked up in cu_seqlens_q
+void fast_topk_transform_fused(const Tensor& score, const Tensor& lengths, Tensor& dst_page_table, const Tensor& src_page_table,
+                               const Tensor& cu_seqlens_q, const std::optional<Tensor>& row_starts) {
+  const bool decode = !row_starts && src_page_table.dim() == 2 && score.dim() == 2 && src_page_table.size(0) == score.size(0);
+  topk_select("fast_topk_transform_fused", score, lengths, row_starts, dst_page_table, std::nullopt, &src_page_table,
+              decode ? nullptr : &cu_seqlens_q, src_page_table.dim() == 2 ? src_page_table.size(0) + 1 : -1, 2048, 1,
+              SGLK_TOPK_PAGE_TABLE);
+}
+
+void fast_topk_transform_ragged_fused(const Tensor& score, const Tensor& lengths, Tensor& topk_indices_ragged,
+                                      const Tensor& topk_indices_offset, const std::optional<Tensor>& row_starts) {
+  topk_select("fast_topk_transform_ragged_fused", score, lengths, row_starts, topk_indices_ragged, std::nullopt, nullptr,
+              &topk_indices_offset, score.dim() == 2 ? score.size(0) : -1, 2048, 1, SGLK_TOPK_OFFSET);
+}
+
+void topk_transform_512(const Tensor& scores, const Tensor& seq_lens, const Tensor& page_tables, Tensor& out_page_indices,
+                        int64_t page_size, const std::optional<Tensor>& out_raw_indices) {
+  const char* op = "topk_transform_512";
+  TORCH_CHECK(out_page_indices.dim() == 2 && out_page_indices.size(1) >= 1 && out_page_indices.size(1) <= 2048, op,
+              ": out_page_indices must be [B, topk] with topk in 1..2048");
+  TORCH_CHECK(page_size >= 1 && page_size <= (1 << 20) && (page_size & (page_size - 1)) == 0, op,
+              ": page_size must be a power of two");
+  topk_select(op, scores, seq_lens, std::nullopt, out_page_indices, out_raw_indices, &page_tables, nullptr, 0,
+              out_page_indices.size(1), page_size, SGLK_TOPK_PAGED);
+}
+
+// (metadata is the reference's scheduling hint: accepted and ignored)
+void topk_transform_512_v2(const Tensor& scores, const Tensor& seq_lens, const Tensor& page_tables, Tensor& out_page_indices,
+                           int64_t page_size, const Tensor& metadata, const std::optional<Tensor>& out_raw_indices) {
+  topk_transform_512(scores, seq_lens, page_tables, out_page_indices, page_size, out_raw_indices);
+}
+
 // ---- fp8 / int8 per-token x per-channel GEMM (declared only: reference
 // include/sgl_kernel_ops.h:567-580; call order python/sgl_kernel/gemm.py:13-42) -----------------
 
@@ -1844,6 +1928,25 @@ TORCH_LIBRARY_FRAGMENT(sgl_kernel, m) {
       "fp8_paged_mqa_logits(Tensor q_fp8, Tensor kv_cache, Tensor weights, Tensor seq_lens, Tensor block_tables,"
       " Tensor? schedule_metadata, int max_seq_len, bool clean_logits, bool block_layout=False) -> Tensor");
   m.impl("fp8_paged_mqa_logits", c10::kCUDA, &fp8_paged_mqa_logits);
+  // authored: the reference's schemas of python/sgl_kernel/top_k.py (src/torch_extension_sycl.cc)
+  m.def("fast_topk(Tensor score, Tensor! indices, Tensor lengths, Tensor? row_starts) -> ()");
+  m.impl("fast_topk", c10::kCUDA, &fast_topk);
+  m.def(
+      "fast_topk_transform_fused(Tensor score, Tensor lengths, Tensor! dst_page_table, Tensor src_page_table,"
+      " Tensor cu_seqlens_q, Tensor? row_starts) -> ()");
+  m.impl("fast_topk_transform_fused", c10::kCUDA, &fast_topk_transform_fused);
+  m.def(
+      "fast_topk_transform_ragged_fused(Tensor score, Tensor lengths, Tensor! topk_indices_ragged,"
+      " Tensor topk_indices_offset, Tensor? row_starts) -> ()");
+  m.impl("fast_topk_transform_ragged_fused", c10::kCUDA, &fast_topk_transform_ragged_fused);
+  m.def(
+      "topk_transform_512(Tensor scores, Tensor seq_lens, Tensor page_tables, Tensor! out_page_indices, int page_size,"
+      " Tensor? out_raw_indices) -> ()");
+  m.impl("topk_transform_512", c10::kCUDA, &topk_transform_512);
+  m.def(
+      "topk_transform_512_v2(Tensor scores, Tensor seq_lens, Tensor page_tables, Tensor! out_page_indices, int page_size,"
+      " Tensor metadata, Tensor? out_raw_indices) -> ()");
+  m.impl("topk_transform_512_v2", c10::kCUDA, &topk_transform_512_v2);
   // authored: reference include/sgl_kernel_ops.h:567-580 + python/sgl_kernel/gemm.py:13-42
   m.def(
       "fp8_scaled_mm(Tensor mat_a, Tensor mat_b, Tensor scales_a, Tensor scales_b, ScalarType out_dtype,"

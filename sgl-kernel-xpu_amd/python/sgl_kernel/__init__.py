@@ -78,6 +78,13 @@ from sgl_kernel.sampling import (  # noqa: E402
     top_p_renorm_probs,
     top_p_sampling_from_probs,
 )
+from sgl_kernel.top_k import (  # noqa: E402
+    fast_topk_transform_fused,
+    fast_topk_transform_ragged_fused,
+    fast_topk_v2,
+    topk_transform_512,
+    topk_transform_512_v2,
+)
 from sgl_kernel.utils import get_device_capability, is_gfx950_arch, is_xe2_arch  # noqa: E402
 from sgl_kernel.version import __version__  # noqa: E402
 
@@ -92,7 +99,7 @@ _OUT_OF_SCOPE = frozenset(
     build_tree_kernel_efficient causal_conv1d causal_conv1d_fn_xpu causal_conv1d_update_xpu
     compile_inkling_attn_prologue compress_norm_rope_store convert_vertical_slash_indexes
     convert_vertical_slash_indexes_mergehead cutlass_fp4_group_mm cutlass_scaled_fp4_mm
-    embedding_lora_a_fwd fast_topk_transform_fused fast_topk_transform_ragged_fused fast_topk_v2
+    embedding_lora_a_fwd
     flash_compress128_decode flash_compress128_prefill flash_compress4_decode
     flash_compress4_prefill flash_mla_sparse_fwd flash_mla_with_kvcache
     fused_causal_conv1d_update_decode fused_decode_sconv_metadata
@@ -107,7 +114,7 @@ _OUT_OF_SCOPE = frozenset(
     precompute_helion_decode_metadata precompute_helion_extend_metadata qkv_lora_b_fwd
     save_intermediate_conv_windows scaled_fp4_experts_quant scaled_fp4_quant segment_packbits
     sgemm_lora_a_fwd sgemm_lora_b_fwd sgl_per_token_group_quant_fp4 sparse_attn_func
-    sparse_attn_varlen_func topk_transform_512 topk_transform_512_v2 track_conv_indices
+    sparse_attn_varlen_func track_conv_indices
     transfer_kv_all_layer transfer_kv_all_layer_direct_lf_pf transfer_kv_all_layer_lf_pf
     transfer_kv_all_layer_lf_ph transfer_kv_all_layer_mla transfer_kv_all_layer_mla_lf_pf
     transfer_kv_direct transfer_kv_per_layer transfer_kv_per_layer_direct_pf_lf
