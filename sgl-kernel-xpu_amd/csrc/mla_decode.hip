@@ -275,7 +275,11 @@ __global__ __launch_bounds__(kThreads, 2) void mla_decode_kernel(MlaParams p, co
     char* base = smem + st * kStageBytes;
     const int tok0 = t * kTile;
     // a 32-token tile touches one page (PAGE >= 32) or two (PAGE == 16); if the second half of the tile is
-    // past the sequence its page entry may be unused: re-use the first page (those rows are masked)
+    // past the sequence its page entry may be unused: re-use the first page (those rows are masked).
+    // Rows past the sequence load the last key's row instead of their own: their weight is 0, but what the cache holds
+    // there is anything (an unwritten pool, a recycled page) and 0 x NaN would reach O. The last key lies in this tile,
+    // in the half the row's page pointer names (src1 = src0 whenever the second half holds no key).
+    const int last = seq - 1;
     const int pg0 = table[tok0 >> p.page_shift];
     int pg1 = pg0;
     if (p.page_shift == 4 && tok0 + 16 < seq) pg1 = table[(tok0 + 16) >> 4];
@@ -287,14 +291,16 @@ __global__ __launch_bounds__(kThreads, 2) void mla_decode_kernel(MlaParams p, co
       const int rg = (wave & 1) * 4 + i;
       const int row = rg * 4 + (lane >> 4);
       const int ch = (lane & 15) ^ sw_main(row);
-      const int in_page = (tok0 + row) & page_mask;
+      const int tok = tok0 + row;
+      const int in_page = (tok < last ? tok : last) & page_mask;
       const char* src = ((wave & 1) == 0 ? src0 : src1) + in_page * kRowBytes + cb * 256 + ch * 16;
       __builtin_amdgcn_global_load_lds(SGLK_GLB(src), SGLK_LDS(base + cb * 8192 + rg * 1024), 16, 0, 0);
     }
     if (wave < 4) {
       const int row = wave * 8 + (lane >> 3);
       const int ch = (lane & 7) ^ ((row >> 1) & 7);
-      const int in_page = (tok0 + row) & page_mask;
+      const int tok = tok0 + row;
+      const int in_page = (tok < last ? tok : last) & page_mask;
       const char* src = (wave < 2 ? src0 : src1) + in_page * kRowBytes + 1024 + ch * 16;
       __builtin_amdgcn_global_load_lds(SGLK_GLB(src), SGLK_LDS(base + kMainBytes + wave * 1024), 16, 0, 0);
     }
@@ -1522,6 +1528,29 @@ __global__ __launch_bounds__(kThreads2, 1) void mla_rows128z_kernel(MlaParams p,
 #pragma unroll
         for (int v = 0; v < 16; ++v)
           if (t * kTile + (v & 3) + 8 * (v >> 2) + 4 * r.u >= kv_row) s[v] = -INFINITY;
+      }
+      // The sequence's last tile: its rows past the last key hold whatever the cache holds there (an unwritten pool, a
+      // recycled page: NaN / Inf are possible) and P . V would multiply them by weight 0 - 0 x NaN = NaN in O. The DMA's
+      // lane offsets are loop invariants, so the rows are not redirected on the way in as in the kernel above: between this
+      // tile's QK^T (whose logits of those rows were just masked) and its P . V every working wave zeroes them in LDS - all
+      // of them, so that it needs no barrier: it reads back its own stores, the other waves store the same zeros, and a
+      // wave still in QK^T reads rows it masks. Once per sequence. (asm stores with their own wait, as the DMA: see dma_s)
+      const int n_keys = seq - t * kTile;
+      if (n_keys < kTile) {
+        int tz = threadIdx.x;
+        asm volatile("" : "+v"(tz));
+        const uint32_t sb = lds_base + (uint32_t)((j & 3) * kStageBytes);
+        const uint32_t za = sb + (uint32_t)(((tz >> 4) & 3) * 8192 + (tz & 15) * 16);  // lane: column block, 16-byte chunk
+        const v4i zero = {0, 0, 0, 0};
+        for (int r = n_keys; r < kTile; ++r)
+          asm volatile("ds_write_b128 %0, %1" ::"v"(za + (uint32_t)(r * 256)), "v"(zero) : "memory");
+#pragma unroll
+        for (int r8 = 0; r8 < kTile; r8 += 8) {  // rope rows r8 .. r8 + 7, 128 bytes each
+          const int rr = r8 + ((tz >> 3) & 7);
+          const uint32_t ar = sb + (uint32_t)(kMainBytes + rr * 128 + (tz & 7) * 16);
+          if (rr >= n_keys) asm volatile("ds_write_b128 %0, %1" ::"v"(ar), "v"(zero) : "memory");
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       }
     }
   };
