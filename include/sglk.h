@@ -280,6 +280,24 @@ SGLK_API int sglk_flash_mla_prefill(sglk_stream_t stream, void* out, const void*
                                     int64_t q_pe_stride_h, int64_t cache_page_stride, int64_t table_stride,
                                     float sm_scale, int causal, int dtype);
 
+/* ---- sparse MLA prefill -------------------------------------------------------
+ * flash_mla_sparse_prefill: reference schema src/torch_extension_sycl.cc:385-388, wrapper
+ * python/sgl_kernel/attention.py:356-397, meaning tests/test_flash_mla_sparse_fwd.py:26-68.
+ * q [s_q, H, d_qk] and kv [s_kv, d_qk] bf16 (d_qk 512 or 576, strides in elements, rows contiguous and 16-byte
+ * aligned), indices [s_q, topk] int32 (indices_stride elements between two tokens' lists). Slot j of token t is
+ * valid iff 0 <= indices[t, j] < s_kv and (topk_length is NULL or j < topk_length[t]); over the valid slots
+ *   P = sm_scale * q[t,h] . kv[idx],  max_logits[t,h] = max P (f32, -inf without a valid slot),
+ *   lse[t,h] = ln sum exp P (f32, +inf without one),  out[t,h,:512] = sum exp(P - lse') kv[idx][:512] (bf16, 0 without
+ *   one),  lse' = logaddexp(lse, attn_sink[h]) where attn_sink (f32 [H]) is given, else lse.
+ * out / max_logits / lse are contiguous. A kv row that no valid slot names is never read. sm_scale > 0, d_v = 512,
+ * dtype SGLK_BF16; anything else returns SGLK_EINVAL before any HIP call. No workspace is used. */
+SGLK_API int sglk_flash_mla_sparse_prefill(sglk_stream_t stream, void* out, float* max_logits, float* lse, const void* q,
+                                           const void* kv, const int32_t* indices, const float* attn_sink,
+                                           const int32_t* topk_length, int64_t s_q, int64_t num_heads, int64_t d_qk,
+                                           int64_t d_v, int64_t s_kv, int64_t topk, int64_t q_stride_t,
+                                           int64_t q_stride_h, int64_t kv_stride, int64_t indices_stride,
+                                           float sm_scale, int dtype);
+
 /* ---- MoE routing, data movement and W4A16 grouped GEMM -----------------------
  * topk_softmax: reference src/sycl/TopKSoftMax.cpp:584-644 (schema torch_extension_sycl.cc:53).
  *   gating [tokens, experts] (F16/BF16/F32) -> topk_weights fp32 [tokens, k], topk_indices int32. */

@@ -12,7 +12,7 @@ Incremental: a source is recompiled when it, a header or this script is newer
 than its object.
 
 After compiling, the ISA of the kernels that manage registers or wait counters by hand
-(mla_decode.hip, gemm_8bit.hip) is checked (check_isa below): a compiler that spills or parks
+(mla_decode.hip, gemm_8bit.hip, mla_sparse.hip, ...: ISA_CHECKED) is checked (check_isa below): a compiler that spills or parks
 values in the accumulator registers those kernels own would give silently wrong results, so a
 failed check fails the build. Validated with ROCm 7.2.0 (AMD clang 20, /opt/rocm/bin/hipcc).
 
@@ -59,6 +59,7 @@ FILE_FLAGS = {
     "mla_decode.hip": ["-fno-slp-vectorize"],
     "moe_fp8bw.hip": ["-fno-slp-vectorize"],
     "mqa_logits.hip": ["-fno-slp-vectorize"],
+    "mla_sparse.hip": ["-fno-slp-vectorize"],
 }
 
 
@@ -79,7 +80,7 @@ def run(cmd):
 
 # sources whose device assembly is kept next to the object (-save-temps=obj) for check_isa
 ISA_CHECKED = ("mla_decode.hip", "gemm_8bit.hip", "attn_fwd.hip", "moe_w4a16.hip", "moe_bf16.hip", "moe_persist.hip",
-               "moe_fp8bw.hip", "mqa_logits.hip", "topk_select.hip")
+               "moe_fp8bw.hip", "mqa_logits.hip", "topk_select.hip", "mla_sparse.hip")
 
 
 def _asm_path(src_name, obj_dir=None):
@@ -191,7 +192,9 @@ def check_isa(verbose=True):
                           # (mqa_ragged counts its LDS-DMA and its stores by hand; mqa_paged's register ring must stay in registers)
                           ("mqa_logits.hip", r"mqa_ragged_kernelI"), ("mqa_logits.hip", r"mqa_paged_kernelI"),
                           # (topk_select is sized for 128 registers, two 512-thread workgroups a CU, with 4 loads in flight a lane)
-                          ("topk_select.hip", r"topk_select_kernelE")):
+                          ("topk_select.hip", r"topk_select_kernelE"),
+                          # (mla_sparse counts its LDS-DMA ring by hand and is sized for two 256-register waves per SIMD)
+                          ("mla_sparse.hip", r"mla_sparse_kernelI")):
         path = _asm_path(src_name)
         if not os.path.exists(path):
             problems.append("%s missing" % path)
@@ -202,7 +205,10 @@ def check_isa(verbose=True):
             # attn_prefill_kernel at d = 256 takes the whole register file and may park values the tile loop never touches in
             # scratch - stored in front of the loop, reloaded behind it. That is harmless; a scratch access INSIDE a loop (the
             # assembler's block annotations say which blocks those are) is the failure this check exists for.
-            loop_only = src_name == "attn_fwd.hip" and "attn_prefill_kernel" in pat and "Li256E" in name
+            # The same holds for the 128-head form of mla_sparse_kernel (W = 1: Q^T 72 + O 128 registers a lane), which parks
+            # what only its epilogue reads (the lane's head for the sink, output offsets).
+            loop_only = (src_name == "attn_fwd.hip" and "attn_prefill_kernel" in pat and "Li256E" in name) or \
+                        (src_name == "mla_sparse.hip" and "mla_sparse_kernelILi1E" in name)
             in_loop = False
             for ln in body:
                 if "; in Loop:" in ln or "Loop Header:" in ln:

@@ -754,6 +754,57 @@ int64_t flash_mla_prefill_get_workspace_size(int64_t max_seq_len, int64_t num_ba
   return sglk_flash_mla_prefill_workspace_size(max_seq_len, num_batches, num_heads, page_size, num_kv_splits);
 }
 
+// ---- flash_mla_sparse_prefill (reference schema torch_extension_sycl.cc:385-388; wrapper attention.py:356-397) ----
+
+void flash_mla_sparse_prefill(Tensor& out, Tensor& max_logits, Tensor& lse, Tensor& q, Tensor& kv, Tensor& indices,
+                              double sm_scale, int64_t head_dim_v, const std::optional<Tensor>& attn_sink,
+                              const std::optional<Tensor>& topk_length) {
+  CHECK_GPU(out);
+  CHECK_GPU(max_logits);
+  CHECK_GPU(lse);
+  CHECK_GPU(q);
+  CHECK_GPU(kv);
+  CHECK_GPU(indices);
+  TORCH_CHECK(q.dim() == 3 && kv.dim() == 3 && indices.dim() == 3 && out.dim() == 3,
+              "flash_mla_sparse_prefill: q, kv, indices and out must be 3-D");
+  const int64_t s_q = q.size(0), H = q.size(1), d_qk = q.size(2), s_kv = kv.size(0), topk = indices.size(2);
+  TORCH_CHECK(d_qk == 512 || d_qk == 576, "flash_mla_sparse_prefill: d_qk must be 512 or 576, got ", d_qk);
+  TORCH_CHECK(head_dim_v == 512, "flash_mla_sparse_prefill: d_v must be 512, got ", head_dim_v);
+  TORCH_CHECK(kv.size(1) == 1 && kv.size(2) == d_qk, "flash_mla_sparse_prefill: kv must be [s_kv, 1, d_qk = ", d_qk, "]");
+  TORCH_CHECK(indices.size(0) == s_q && indices.size(1) == 1, "flash_mla_sparse_prefill: indices must be [s_q, 1, topk]");
+  TORCH_CHECK(q.scalar_type() == at::kBFloat16 && kv.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16,
+              "flash_mla_sparse_prefill: q, kv and out must be BFloat16");
+  TORCH_CHECK(indices.scalar_type() == at::kInt, "flash_mla_sparse_prefill: indices must be int32");
+  TORCH_CHECK(q.stride(2) == 1 && kv.stride(2) == 1 && indices.stride(2) == 1,
+              "flash_mla_sparse_prefill: the last dimension of q, kv and indices must be contiguous");
+  TORCH_CHECK(out.size(0) == s_q && out.size(1) == H && out.size(2) == 512 && out.is_contiguous(),
+              "flash_mla_sparse_prefill: out must be a contiguous [s_q, H, 512] tensor");
+  for (const Tensor* t : {&max_logits, &lse})
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 2 && t->size(0) == s_q && t->size(1) == H && t->is_contiguous(),
+                "flash_mla_sparse_prefill: max_logits and lse must be contiguous float32 [s_q, H] tensors");
+  const float* sink = nullptr;
+  if (attn_sink.has_value()) {
+    CHECK_GPU(*attn_sink);
+    TORCH_CHECK(attn_sink->scalar_type() == at::kFloat && attn_sink->dim() == 1 && attn_sink->size(0) == H &&
+                    attn_sink->is_contiguous(),
+                "flash_mla_sparse_prefill: attn_sink must be a contiguous float32 [H] tensor");
+    sink = attn_sink->data_ptr<float>();
+  }
+  const int32_t* lengths = nullptr;
+  if (topk_length.has_value()) {
+    CHECK_GPU(*topk_length);
+    TORCH_CHECK(topk_length->scalar_type() == at::kInt && topk_length->dim() == 1 && topk_length->size(0) == s_q &&
+                    topk_length->is_contiguous(),
+                "flash_mla_sparse_prefill: topk_length must be a contiguous int32 [s_q] tensor");
+    lengths = topk_length->data_ptr<int32_t>();
+  }
+  const c10::OptionalDeviceGuard guard(q.device());
+  SGLK_CALL(sglk_flash_mla_sparse_prefill(stream_of(q), out.data_ptr(), max_logits.data_ptr<float>(), lse.data_ptr<float>(),
+                                          q.data_ptr(), kv.data_ptr(), indices.data_ptr<int32_t>(), sink, lengths, s_q, H,
+                                          d_qk, head_dim_v, s_kv, topk, q.stride(0), q.stride(1), kv.stride(0),
+                                          indices.stride(0), (float)sm_scale, SGLK_BF16));
+}
+
 // ---- MoE (reference src/sycl/TopKSoftMax.cpp:584-644, MoEAlign.cpp:313-383, MoEPrepareInputs.cpp,
 //           GroupGemmW4A16Xe20.cpp:92-283) ----------------------------------------------------------
 
@@ -2016,6 +2067,11 @@ TORCH_LIBRARY_FRAGMENT(sgl_kernel, m) {
       "Tensor! cu_seqlens_q, Tensor! seq_lens, int max_seqlen_q, "
       "Tensor! page_table, Tensor! workspace, float sm_scale, bool causal, int num_kv_splits) -> ()");
   m.impl("flash_mla_prefill", c10::kCUDA, &flash_mla_prefill);
+  m.def(
+      "flash_mla_sparse_prefill(Tensor! out, Tensor! max_logits, Tensor! lse, Tensor! q, Tensor! kv, "
+      "Tensor! indices, float sm_scale, int head_dim_v, "
+      "Tensor? attn_sink=None, Tensor? topk_length=None) -> ()");
+  m.impl("flash_mla_sparse_prefill", c10::kCUDA, &flash_mla_sparse_prefill);
 
   // reference src/torch_extension_sycl.cc:53, :199-203, :214-229
   m.def("topk_softmax(Tensor! topk_weights, Tensor! topk_indices, Tensor gating_output, bool renormalize) -> ()");

@@ -2,7 +2,7 @@
 
 Contract (reference python/sgl_kernel/attention.py): the public names and parameters of `flash_mla_decode`
 (:54-62), `flash_mla_get_workspace_size` (:128-146), `flash_mla_prefill` (:149-161) and
-`flash_mla_prefill_get_workspace_size` (:236-247); latent width 512 + rope width 64, at most 128 heads, 16-bit
+`flash_mla_prefill_get_workspace_size` (:236-247) and `flash_mla_sparse_fwd` (:356-397); latent width 512 + rope width 64, at most 128 heads, 16-bit
 dtypes, int32 `seq_lens` / `page_table` (:77-111); a page table whose width covers whole 128-token spans (:101);
 output [rows, heads, 512] in the query dtype (:113-119); the op argument order of
 src/torch_extension_sycl.cc:364-383.
@@ -138,3 +138,39 @@ def flash_mla_prefill_get_workspace_size(max_seq_len: int, num_batches: int, num
     """This library's prefill keeps everything on chip: the answer is 0 (the op is still asked, as the reference does)."""
     _check_positive("flash_mla_prefill_get_workspace_size", max_seq_len=max_seq_len, num_batches=num_batches)
     return _ops.flash_mla_prefill_get_workspace_size.default(max_seq_len, num_batches, num_heads, page_size, num_kv_splits)
+
+
+def flash_mla_sparse_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tensor, sm_scale: float, d_v: int = 512,
+                         attn_sink: Optional[torch.Tensor] = None,
+                         topk_length: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Sparse MLA prefill: token t attends to the kv rows indices[t, 0, :] names (reference attention.py:356-397).
+
+    q [s_q, h_q, d_qk] and kv [s_kv, 1, d_qk] bf16 with d_qk 512 or 576, indices [s_q, 1, topk] int32. Slot j of token t
+    is valid iff 0 <= indices[t, 0, j] < s_kv and (topk_length is None or j < topk_length[t]). Over the valid slots
+    P = sm_scale * q[t, h] . kv[idx]; returns (out [s_q, h_q, 512] bf16, max_logits [s_q, h_q] f32 = max P, lse [s_q, h_q]
+    f32 = ln sum exp P) with out = sum exp(P - lse') kv[idx][:512], lse' = logaddexp(lse, attn_sink[h]) where attn_sink
+    (f32 [h_q]) is given (it changes neither lse nor max_logits). A token without a valid slot gets out = 0, lse = +inf,
+    max_logits = -inf. Unlike the reference, kv rows that no valid slot names are never read."""
+    who = "flash_mla_sparse_fwd"
+    assert q.ndim == 3 and kv.ndim == 3 and indices.ndim == 3, f"{who}: q, kv and indices must be 3D tensors"
+    s_q, h_q, d_qk = q.shape
+    assert d_qk in (LATENT_DIM, LATENT_DIM + ROPE_DIM), f"{who}: d_qk must be 512 or 576, got {d_qk}"
+    assert d_v == LATENT_DIM, f"{who}: d_v can only be {LATENT_DIM}, got {d_v}"
+    assert kv.shape[1:] == (1, d_qk), f"{who}: kv must be [s_kv, 1, {d_qk}], got {tuple(kv.shape)}"
+    assert indices.shape[:2] == (s_q, 1), f"{who}: indices must be [s_q={s_q}, 1, topk], got {tuple(indices.shape)}"
+    assert q.dtype == kv.dtype == torch.bfloat16, f"{who}: q and kv must be bf16, got {q.dtype} and {kv.dtype}"
+    _check_int32(who, indices=indices)
+    if attn_sink is not None:
+        assert attn_sink.dtype == torch.float32 and attn_sink.shape == (h_q,), f"{who}: attn_sink must be float32 [{h_q}]"
+    if topk_length is not None:
+        _check_int32(who, topk_length=topk_length)
+        assert topk_length.shape == (s_q,), f"{who}: topk_length must be [{s_q}], got {tuple(topk_length.shape)}"
+
+    out = q.new_empty((s_q, h_q, d_v))
+    max_logits = q.new_empty((s_q, h_q), dtype=torch.float32)
+    lse = q.new_empty((s_q, h_q), dtype=torch.float32)
+    if s_q > 0:
+        _ops.flash_mla_sparse_prefill.default(
+            out, max_logits, lse, _inner_unit_stride(q), _inner_unit_stride(kv), _inner_unit_stride(indices), sm_scale, d_v,
+            None if attn_sink is None else attn_sink.contiguous(), None if topk_length is None else topk_length.contiguous())
+    return out, max_logits, lse
