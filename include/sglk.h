@@ -61,9 +61,10 @@ SGLK_API const char* sglk_version(void);
 SGLK_API const char* sglk_arch(void);
 /* ABI revision of this header. It is raised whenever an entry point changes its parameter list or a workspace its layout or
  * size (5: sglk_moe_grouped_mm_w4a16_act takes row_map / src_rows; the flash_mla_decode workspace holds 16-byte merge
- * counters and, above 64 heads, 128-row fragment slabs). A caller built against another revision must not call in: compare
+ * counters and, above 64 heads, 128-row fragment slabs; 6: sglk_flash_mla_sparse_decode and its split / workspace rules
+ * are new). A caller built against another revision must not call in: compare
  * sglk_abi_version() with the SGLK_ABI_VERSION it was compiled with. */
-#define SGLK_ABI_VERSION 5
+#define SGLK_ABI_VERSION 6
 SGLK_API int sglk_abi_version(void);
 
 /* Row addressing of a 2-D / 3-D last-dim-contiguous tensor:
@@ -297,6 +298,39 @@ SGLK_API int sglk_flash_mla_sparse_prefill(sglk_stream_t stream, void* out, floa
                                            int64_t d_v, int64_t s_kv, int64_t topk, int64_t q_stride_t,
                                            int64_t q_stride_h, int64_t kv_stride, int64_t indices_stride,
                                            float sm_scale, int dtype);
+
+/* ---- sparse MLA decode over the packed fp8 cache -------------------------------
+ * flash_mla_sparse_decode: reference schema src/torch_extension_sycl.cc:371-374, wrapper
+ * python/sgl_kernel/attention.py:250-353, meaning tests/test_flash_mla_with_kvcache.py.
+ * q [batch, s_q, H, 512] bf16 (strides in elements, rows contiguous and 16-byte aligned); indices [batch, s_q, topk] and
+ * extra_indices [batch, s_q, extra_topk] int32, contiguous; topk_length / extra_topk_length int32 [batch] or NULL
+ * (negative counts as 0, more than the list as the list); attn_sink f32 [H] or NULL. A cache is num_pages pages of
+ * page_bytes bytes (>= 584 page_size, a multiple of 16, base 16-byte aligned); token t of the page at byte P has 448
+ * e4m3 bytes (7 tiles of 64) and 64 bf16 at P + 576 t, and 7 UE8M0 scale bytes (+ 1 pad) at P + 576 page_size + 8 t;
+ * its row is [e4m3 * 2^(scale - 127), the 64 bf16]: 512 columns, K and V at once. Token index i is slot i % page_size
+ * of page i / page_size. The extra cache (with its own page size) and extra_indices come together or not at all.
+ * The slot list of query token (b, s) is indices[b, s, :] followed by extra_indices[b, s, :]; a slot is valid iff
+ * 0 <= idx < num_pages * page_size of its cache and it lies in front of its list's length. Over the valid slots
+ *   P = sm_scale * q[b,s,h] . row,  lse[b,h,s] = ln sum exp P (f32 [batch, H, s_q]; +inf without a valid slot),
+ *   out[b,s,h,:] = sum exp(P - lse') row (bf16 [batch, s_q, H, 512], contiguous; 0 without a valid slot),
+ *   lse' = logaddexp(lse, attn_sink[h]) where attn_sink is given, else lse.
+ * A cache token that no valid slot names is never read (data or scales). num_splits workgroups share a token's slots
+ * (< 1: sglk_mla_sparse_decode_auto_splits(batch * s_q, ceil(H / 128), topk + extra_topk), host-only arithmetic on the
+ * nominal list lengths); more than one split needs `workspace` (16-byte aligned) of
+ * sglk_mla_sparse_decode_workspace_size(batch * s_q, H, topk, extra_topk, num_splits) bytes, which holds nothing
+ * between calls. sm_scale > 0; anything else returns SGLK_EINVAL before any HIP call. */
+SGLK_API int64_t sglk_mla_sparse_decode_auto_splits(int64_t tokens, int64_t head_blocks, int64_t slots);
+SGLK_API int64_t sglk_mla_sparse_decode_workspace_size(int64_t tokens, int64_t num_heads, int64_t topk,
+                                                       int64_t extra_topk, int64_t num_splits);
+SGLK_API int sglk_flash_mla_sparse_decode(sglk_stream_t stream, void* out, float* lse, const void* q, const void* k_cache,
+                                          const int32_t* indices, const int32_t* topk_length, const void* extra_k_cache,
+                                          const int32_t* extra_indices, const int32_t* extra_topk_length,
+                                          const float* attn_sink, void* workspace, int64_t workspace_bytes,
+                                          int64_t batch, int64_t s_q, int64_t num_heads, int64_t topk, int64_t extra_topk,
+                                          int64_t q_stride_b, int64_t q_stride_s, int64_t q_stride_h, int64_t num_pages,
+                                          int64_t page_size, int64_t page_bytes, int64_t extra_num_pages,
+                                          int64_t extra_page_size, int64_t extra_page_bytes, float sm_scale,
+                                          int64_t num_splits);
 
 /* ---- MoE routing, data movement and W4A16 grouped GEMM -----------------------
  * topk_softmax: reference src/sycl/TopKSoftMax.cpp:584-644 (schema torch_extension_sycl.cc:53).

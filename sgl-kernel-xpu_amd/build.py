@@ -60,6 +60,7 @@ FILE_FLAGS = {
     "moe_fp8bw.hip": ["-fno-slp-vectorize"],
     "mqa_logits.hip": ["-fno-slp-vectorize"],
     "mla_sparse.hip": ["-fno-slp-vectorize"],
+    "mla_sparse_decode.hip": ["-fno-slp-vectorize"],
 }
 
 
@@ -80,7 +81,7 @@ def run(cmd):
 
 # sources whose device assembly is kept next to the object (-save-temps=obj) for check_isa
 ISA_CHECKED = ("mla_decode.hip", "gemm_8bit.hip", "attn_fwd.hip", "moe_w4a16.hip", "moe_bf16.hip", "moe_persist.hip",
-               "moe_fp8bw.hip", "mqa_logits.hip", "topk_select.hip", "mla_sparse.hip")
+               "moe_fp8bw.hip", "mqa_logits.hip", "topk_select.hip", "mla_sparse.hip", "mla_sparse_decode.hip")
 
 
 def _asm_path(src_name, obj_dir=None):
@@ -194,7 +195,10 @@ def check_isa(verbose=True):
                           # (topk_select is sized for 128 registers, two 512-thread workgroups a CU, with 4 loads in flight a lane)
                           ("topk_select.hip", r"topk_select_kernelE"),
                           # (mla_sparse counts its LDS-DMA ring by hand and is sized for two 256-register waves per SIMD)
-                          ("mla_sparse.hip", r"mla_sparse_kernelI")):
+                          ("mla_sparse.hip", r"mla_sparse_kernelI"),
+                          # (mla_sparse_decode counts the LDS reads of P.V by hand and keeps a tile of raw cache bytes in
+                          #  registers across the products: scratch traffic in the tile loop would serialise both)
+                          ("mla_sparse_decode.hip", r"mla_sparse_decode_kernelI")):
         path = _asm_path(src_name)
         if not os.path.exists(path):
             problems.append("%s missing" % path)
@@ -208,7 +212,8 @@ def check_isa(verbose=True):
             # The same holds for the 128-head form of mla_sparse_kernel (W = 1: Q^T 72 + O 128 registers a lane), which parks
             # what only its epilogue reads (the lane's head for the sink, output offsets).
             loop_only = (src_name == "attn_fwd.hip" and "attn_prefill_kernel" in pat and "Li256E" in name) or \
-                        (src_name == "mla_sparse.hip" and "mla_sparse_kernelILi1E" in name)
+                        (src_name == "mla_sparse.hip" and "mla_sparse_kernelILi1E" in name) or \
+                        (src_name == "mla_sparse_decode.hip" and "mla_sparse_decode_kernelILi1E" in name)
             in_loop = False
             for ln in body:
                 if "; in Loop:" in ln or "Loop Header:" in ln:

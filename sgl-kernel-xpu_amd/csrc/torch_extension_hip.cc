@@ -805,6 +805,90 @@ void flash_mla_sparse_prefill(Tensor& out, Tensor& max_logits, Tensor& lse, Tens
                                           indices.stride(0), (float)sm_scale, SGLK_BF16));
 }
 
+// ---- flash_mla_sparse_decode (reference schema torch_extension_sycl.cc:371-374; wrapper attention.py:250-353) ----
+
+void flash_mla_sparse_decode(Tensor& out, Tensor& lse_out, Tensor& q, Tensor& k_cache, Tensor& indices,
+                             const std::optional<Tensor>& topk_length, const std::optional<Tensor>& extra_k_cache,
+                             const std::optional<Tensor>& extra_indices, const std::optional<Tensor>& extra_topk_length,
+                             const std::optional<Tensor>& attn_sink, double sm_scale, int64_t head_dim_v,
+                             bool is_fp8_kvcache) {
+  const char* who = "flash_mla_sparse_decode: ";
+  CHECK_GPU(out);
+  CHECK_GPU(lse_out);
+  CHECK_GPU(q);
+  CHECK_GPU(k_cache);
+  CHECK_GPU(indices);
+  TORCH_CHECK(is_fp8_kvcache, who, "only the packed fp8 cache is implemented (is_fp8_kvcache must be True)");
+  TORCH_CHECK(head_dim_v == 512, who, "head_dim_v must be 512, got ", head_dim_v);
+  TORCH_CHECK(q.dim() == 4 && q.size(3) == 512 && q.stride(3) == 1 && q.scalar_type() == at::kBFloat16, who,
+              "q must be a BFloat16 [B, s_q, H, 512] tensor with a contiguous last dimension");
+  const int64_t B = q.size(0), s_q = q.size(1), H = q.size(2);
+  TORCH_CHECK(s_q >= 1 && H >= 1, who, "s_q and H must be at least 1");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.dim() == 4 && out.size(0) == B && out.size(1) == s_q &&
+                  out.size(2) == H && out.size(3) == 512 && out.is_contiguous(),
+              who, "out must be a contiguous BFloat16 [B, s_q, H, 512] tensor");
+  TORCH_CHECK(lse_out.scalar_type() == at::kFloat && lse_out.dim() == 3 && lse_out.size(0) == B && lse_out.size(1) == H &&
+                  lse_out.size(2) == s_q && lse_out.is_contiguous(),
+              who, "lse_out must be a contiguous float32 [B, H, s_q] tensor");
+  TORCH_CHECK(extra_k_cache.has_value() == extra_indices.has_value(), who,
+              "extra_k_cache and extra_indices must be given together");
+  TORCH_CHECK(extra_k_cache.has_value() || !extra_topk_length.has_value(), who, "extra_topk_length without an extra cache");
+  auto check_cache = [&](const Tensor& c, const char* name) {
+    CHECK_GPU(c);
+    TORCH_CHECK(c.scalar_type() == at::kFloat8_e4m3fn && c.dim() == 4 && c.size(1) >= 1 && c.size(2) == 1 &&
+                    c.size(3) == 584 && c.stride(3) == 1,
+                who, name, " must be a float8_e4m3fn [pages, page_size, 1, 584] tensor with stride(3) == 1");
+  };
+  auto check_list = [&](const Tensor& t, const char* name) {
+    CHECK_GPU(t);
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 3 && t.size(0) == B && t.size(1) == s_q && t.is_contiguous(), who,
+                name, " must be a contiguous int32 [B, s_q, topk] tensor");
+  };
+  auto vec = [&](const std::optional<Tensor>& t, at::ScalarType ty, int64_t n, const char* name) -> const void* {
+    if (!t.has_value()) return nullptr;
+    CHECK_GPU(*t);
+    TORCH_CHECK(t->scalar_type() == ty && t->dim() == 1 && t->size(0) == n && t->is_contiguous(), who, name,
+                " must be a contiguous 1-D tensor of ", n, " ", ty, " values");
+    return t->data_ptr();
+  };
+  check_cache(k_cache, "k_cache");
+  check_list(indices, "indices");
+  const int64_t topk = indices.size(2);
+  int64_t extra_topk = 0, extra_pages = 0, extra_page_size = 0, extra_page_bytes = 0;
+  const void* extra_cache_ptr = nullptr;
+  const int32_t* extra_idx_ptr = nullptr;
+  if (extra_k_cache.has_value()) {
+    check_cache(*extra_k_cache, "extra_k_cache");
+    check_list(*extra_indices, "extra_indices");
+    extra_topk = extra_indices->size(2);
+    extra_pages = extra_k_cache->size(0);
+    extra_page_size = extra_k_cache->size(1);
+    extra_page_bytes = extra_k_cache->stride(0);
+    extra_cache_ptr = extra_k_cache->data_ptr();
+    extra_idx_ptr = extra_indices->data_ptr<int32_t>();
+  }
+  const void* len = vec(topk_length, at::kInt, B, "topk_length");
+  const void* extra_len = vec(extra_topk_length, at::kInt, B, "extra_topk_length");
+  const void* sink = vec(attn_sink, at::kFloat, H, "attn_sink");
+  if (B == 0) return;
+  if (topk + extra_topk == 0) {  // no slot at all: nothing to launch
+    out.zero_();
+    lse_out.fill_(INFINITY);
+    return;
+  }
+  const c10::OptionalDeviceGuard guard(q.device());
+  // the split count comes from the nominal list lengths (num_splits 0 = this library's rule); partials per call
+  const int64_t ws_bytes = sglk_mla_sparse_decode_workspace_size(B * s_q, H, topk, extra_topk, 0);
+  Tensor ws;
+  if (ws_bytes > 0) ws = at::empty({ws_bytes}, q.options().dtype(at::kByte));
+  SGLK_CALL(sglk_flash_mla_sparse_decode(
+      stream_of(q), out.data_ptr(), lse_out.data_ptr<float>(), q.data_ptr(), k_cache.data_ptr(), indices.data_ptr<int32_t>(),
+      (const int32_t*)len, extra_cache_ptr, extra_idx_ptr, (const int32_t*)extra_len, (const float*)sink,
+      ws_bytes > 0 ? ws.data_ptr() : nullptr, ws_bytes, B, s_q, H, topk, extra_topk, q.stride(0), q.stride(1), q.stride(2),
+      k_cache.size(0), k_cache.size(1), k_cache.stride(0), extra_pages, extra_page_size, extra_page_bytes, (float)sm_scale,
+      0));
+}
+
 // ---- MoE (reference src/sycl/TopKSoftMax.cpp:584-644, MoEAlign.cpp:313-383, MoEPrepareInputs.cpp,
 //           GroupGemmW4A16Xe20.cpp:92-283) ----------------------------------------------------------
 
@@ -2072,6 +2156,11 @@ TORCH_LIBRARY_FRAGMENT(sgl_kernel, m) {
       "Tensor! indices, float sm_scale, int head_dim_v, "
       "Tensor? attn_sink=None, Tensor? topk_length=None) -> ()");
   m.impl("flash_mla_sparse_prefill", c10::kCUDA, &flash_mla_sparse_prefill);
+  m.def(
+      "flash_mla_sparse_decode(Tensor! out, Tensor! lse_out, Tensor! q, Tensor! k_cache, Tensor! indices, "
+      "Tensor? topk_length, Tensor? extra_k_cache, Tensor? extra_indices, Tensor? extra_topk_length, "
+      "Tensor? attn_sink, float sm_scale, int head_dim_v, bool is_fp8_kvcache) -> ()");
+  m.impl("flash_mla_sparse_decode", c10::kCUDA, &flash_mla_sparse_decode);
 
   // reference src/torch_extension_sycl.cc:53, :199-203, :214-229
   m.def("topk_softmax(Tensor! topk_weights, Tensor! topk_indices, Tensor gating_output, bool renormalize) -> ()");

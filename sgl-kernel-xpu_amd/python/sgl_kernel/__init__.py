@@ -24,6 +24,7 @@ from sgl_kernel.attention import (  # noqa: E402
     flash_mla_prefill,
     flash_mla_prefill_get_workspace_size,
     flash_mla_sparse_fwd,
+    flash_mla_with_kvcache,
     merge_state,
     merge_state_v2,
 )
@@ -102,7 +103,7 @@ _OUT_OF_SCOPE = frozenset(
     convert_vertical_slash_indexes_mergehead cutlass_fp4_group_mm cutlass_scaled_fp4_mm
     embedding_lora_a_fwd
     flash_compress128_decode flash_compress128_prefill flash_compress4_decode
-    flash_compress4_prefill flash_mla_with_kvcache
+    flash_compress4_prefill
     fused_causal_conv1d_update_decode fused_decode_sconv_metadata
     fused_draft_extend_sconv_cache fused_extend_sconv_metadata
     fused_gather_scatter_to_sconv_cache fused_k_norm_rope_flashmla

@@ -2,7 +2,7 @@
 
 Contract (reference python/sgl_kernel/attention.py): the public names and parameters of `flash_mla_decode`
 (:54-62), `flash_mla_get_workspace_size` (:128-146), `flash_mla_prefill` (:149-161) and
-`flash_mla_prefill_get_workspace_size` (:236-247) and `flash_mla_sparse_fwd` (:356-397); latent width 512 + rope width 64, at most 128 heads, 16-bit
+`flash_mla_prefill_get_workspace_size` (:236-247), `flash_mla_with_kvcache` (:250-353) and `flash_mla_sparse_fwd` (:356-397); latent width 512 + rope width 64, at most 128 heads, 16-bit
 dtypes, int32 `seq_lens` / `page_table` (:77-111); a page table whose width covers whole 128-token spans (:101);
 output [rows, heads, 512] in the query dtype (:113-119); the op argument order of
 src/torch_extension_sycl.cc:364-383.
@@ -174,3 +174,67 @@ def flash_mla_sparse_fwd(q: torch.Tensor, kv: torch.Tensor, indices: torch.Tenso
             out, max_logits, lse, _inner_unit_stride(q), _inner_unit_stride(kv), _inner_unit_stride(indices), sm_scale, d_v,
             None if attn_sink is None else attn_sink.contiguous(), None if topk_length is None else topk_length.contiguous())
     return out, max_logits, lse
+
+
+def flash_mla_with_kvcache(q: torch.Tensor, k_cache: torch.Tensor, block_table: Optional[torch.Tensor] = None,
+                           cache_seqlens: Optional[torch.Tensor] = None, head_dim_v: int = 512,
+                           tile_scheduler_metadata: Optional[torch.Tensor] = None,
+                           num_splits: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None,
+                           causal: bool = False, is_fp8_kvcache: bool = False, indices: Optional[torch.Tensor] = None,
+                           attn_sink: Optional[torch.Tensor] = None, extra_k_cache: Optional[torch.Tensor] = None,
+                           extra_indices_in_kvcache: Optional[torch.Tensor] = None,
+                           topk_length: Optional[torch.Tensor] = None,
+                           extra_topk_length: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Sparse MLA decode over the DeepSeek-V4 packed fp8 cache (reference attention.py:250-353).
+
+    q [B, s_q, H, 512] bf16; indices [B, s_q, topk] and extra_indices_in_kvcache [B, s_q, extra_topk] int32; topk_length /
+    extra_topk_length int32 [B] (per batch element); attn_sink f32 [H]. k_cache / extra_k_cache are
+    [pages, page_size, 1, 584] float8_e4m3fn with stride(3) == 1 and stride(0) = the page size in bytes: token t of a page
+    holds 448 e4m3 bytes (7 tiles of 64) + 64 bf16 of rope at byte 576 t and 7 UE8M0 scale bytes (+ 1 pad) at
+    576 page_size + 8 t; its row is [e4m3 * 2^(scale - 127), rope], 512 columns, K and V at once. Token index i is slot
+    i % page_size of page i // page_size; the two caches may differ in page size.
+
+    The slot list of query (b, s) is indices[b, s] followed by extra_indices_in_kvcache[b, s]; a slot is valid iff its
+    index lies inside its cache and in front of its list's length. Over the valid slots P = softmax_scale * q . row;
+    returns (out [B, s_q, H, 512] bf16, lse [B, H, s_q] f32 = ln sum exp P) with out = sum exp(P - lse') row and
+    lse' = logaddexp(lse, attn_sink[h]). A query without a valid slot gets out = 0 and lse = +inf: the value the
+    reference's kernel writes and flash_mla_sparse_fwd returns (the reference's Python fallback leaves -inf there and
+    never checks it). Cache tokens that no valid slot names are never read.
+
+    Only this path exists: is_fp8_kvcache must be True, block_table raises NotImplementedError (the reference returns
+    uninitialised memory there), tile_scheduler_metadata / num_splits / causal are refused as in the reference."""
+    who = "flash_mla_with_kvcache"
+    assert tile_scheduler_metadata is None, f"{who}: tile_scheduler_metadata is not supported"
+    assert num_splits is None, f"{who}: num_splits is not supported"
+    assert not causal, f"{who}: causal attention is not supported"
+    if block_table is not None:
+        raise NotImplementedError(f"{who}: the dense block_table path is not implemented; pass indices")
+    assert is_fp8_kvcache, f"{who}: only the packed fp8 cache is implemented (is_fp8_kvcache must be True)"
+    assert q.ndim == 4, f"{who}: q must be 4D [B, s_q, H, D_qk], got {q.ndim}D"
+    assert k_cache.ndim == 4, f"{who}: k_cache must be 4D [num_pages, P, 1, D], got {k_cache.ndim}D"
+    B, s_q, H, d_qk = q.shape
+    assert q.dtype == torch.bfloat16, f"{who}: q.dtype must be bf16, got {q.dtype}"
+    assert d_qk == LATENT_DIM and head_dim_v == LATENT_DIM, f"{who}: D_qk and head_dim_v must be {LATENT_DIM}"
+    assert indices is not None, f"{who}: indices must be provided for the sparse decode path"
+    if (extra_k_cache is None) != (extra_indices_in_kvcache is None):
+        raise AssertionError(f"{who}: extra_k_cache and extra_indices_in_kvcache must be provided together")
+    lists = {"indices": indices}
+    if extra_indices_in_kvcache is not None:
+        lists["extra_indices_in_kvcache"] = extra_indices_in_kvcache
+    _check_int32(who, **lists)
+    for name, t in lists.items():
+        assert t.ndim == 3 and t.shape[:2] == (B, s_q), f"{who}: {name} must be [B={B}, s_q={s_q}, topk]"
+    for name, t in (("topk_length", topk_length), ("extra_topk_length", extra_topk_length)):
+        assert t is None or (t.dtype == torch.int32 and t.shape == (B,)), f"{who}: {name} must be int32 [{B}]"
+    assert attn_sink is None or (attn_sink.dtype == torch.float32 and attn_sink.shape == (H,)), (
+        f"{who}: attn_sink must be float32 [{H}]")
+    if softmax_scale is None:
+        softmax_scale = d_qk ** (-0.5)
+
+    out = q.new_empty((B, s_q, H, head_dim_v))
+    lse = q.new_empty((B, H, s_q), dtype=torch.float32)
+    cont = lambda t: None if t is None else t.contiguous()
+    _ops.flash_mla_sparse_decode.default(out, lse, _inner_unit_stride(q), k_cache, indices.contiguous(), cont(topk_length),
+                                         extra_k_cache, cont(extra_indices_in_kvcache), cont(extra_topk_length),
+                                         cont(attn_sink), softmax_scale, head_dim_v, is_fp8_kvcache)
+    return out, lse
